@@ -1,9 +1,9 @@
 """bench.py - the hot path on N MI355X of one node, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload both|vit|whisper|c4|c5|stub]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload both|vit|whisper|c4|c5|stub] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-BASELINE.json's metric has two halves and the default run times BOTH, each for exactly K steps after W warm-ups:
+BASELINE.json's metric has two halves; `--full` times BOTH, each for exactly K steps after W warm-ups:
   vit     : ViT-B/16 bf16 forward, batch 256 per GPU, 224x224 (BASELINE.json configs[1])
   whisper : Whisper-base log-mel + encoder + 224-step KV-cached greedy decode, 32 x 30 s clips per GPU (configs[2])
   c4      : Whisper large-v2, the same pipeline, 32 clips per GPU = BASELINE configs[3] at --gpus 8 (batch 256 over 8 GPUs)
@@ -11,6 +11,13 @@ BASELINE.json's metric has two halves and the default run times BOTH, each for e
 One "step" = one pass of the hot path over one per-GPU batch of synthetic input already resident in HBM.
 Rank 0 prints ONE JSON line: the top-level metric fields are the ViT-B/16 leg (the configuration the metric is quoted on
 first), the Whisper leg is the "whisper" object and is repeated under config.legs / roofline.whisper / cpu_baseline.whisper.
+A plain run (no `--full`) does only what that headline needs: it sets up, warms up, times the K steps of the first leg
+(`--workload both`: the ViT-B/16 leg alone) and prints the line.  `--full` adds everything else, each outside the timed
+region: the Whisper-base leg of `--workload both`, the per-kernel event passes and roofline figures of every leg, the
+CPU baselines (rank 0, N = 1) and the exact-mode extra of the Whisper-base leg.
+`--dump-outputs DIR` writes what the timed path returned at its last timed step (rank 0, after any gather) as
+DIR/<leg>_<what>.npy (float32, or float64 for token ids; a fixed, seeded sample beyond 64 MB in all).  The weights and
+inputs are seeded, so two runs with the same arguments see identical inputs.
 For N > 1 every rank runs its own shard (weak scaling, no data-path collective) and each step ends with the product's
 one gather of the outputs (pytorch_models.dp.OutputGatherer: RCCL all_gather over xGMI under backend "nccl").
 `--gpus N` without a torch.distributed environment starts the N ranks itself (child processes, before any HIP call).
@@ -35,6 +42,9 @@ import torch.distributed as dist  # noqa: E402
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md "Peak BF16/FP16 MFMA"
 PEAK_HBM_GBS = 8000.0
 PROFILE_DIRS = ("r03", "r02", "r01")  # committed rocprofv3 PMC summaries, newest first
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+BOTH_METRIC = ("ViT-B/16 images/s & Whisper-base audio-sec/s (BASELINE.json metric; value / unit / ms_per_step = the "
+               "ViT-B/16 leg of configs[1], the Whisper-base leg of configs[2] is the \"whisper\" object)")
 
 
 def host_cores() -> int:
@@ -91,15 +101,32 @@ def cpu_baseline_vit(seconds_budget: float = 20.0) -> dict:
 
 
 def timed_steps(step, args, world):
-    """W untimed warm-ups, then EXACTLY K steps between barrier + synchronize pairs; seconds of the timed region."""
+    """W untimed warm-ups, then EXACTLY K steps between barrier + synchronize pairs; (seconds of the timed region, what the
+    last timed step returned)."""
     for _ in range(args.warmup):
         step()
     sync(world)
+    out = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     sync(world)
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
+
+
+def dump_outputs(outs: dict, d: str) -> None:
+    """--dump-outputs: every array as d/<name>.npy; an array over its share of DUMP_BYTES is replaced by a fixed, seeded
+    sample of its elements (flattened, in index order)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outs))
+    for name, a in outs.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 VIT_LEGS = {
@@ -130,12 +157,13 @@ def run_vit(args, rank, world, device, leg="vit"):
         return gather(out) if gather is not None else out
 
     with torch.no_grad():
-        dt = timed_steps(step, args, world)
-        # roofline leg: the SAME K steps once more with two HIP events around every launch (recorded on the launch
+        dt, out = timed_steps(step, args, world)
+        dump = {f"{leg}_features": out.float().cpu().numpy()} if args.dump_outputs and rank == 0 else {}
+        # --full, roofline leg: the SAME K steps once more with two HIP events around every launch (recorded on the launch
         # stream).  Kept out of the timed region: the event records themselves open ~10 us gaps between kernels
         # (measured: 6 % of the step), which would tax `value` without changing the per-kernel durations.
         log = None
-        if rank == 0:
+        if rank == 0 and args.full:
             # ... and with the encoder on ONE stream: the product default runs the two halves of the batch on two streams
             # (pytorch_models/transformer.py, Encoder.forward), where the events of concurrent kernels overlap and a per-kernel
             # duration says nothing about the kernel.  Same kernels, same tile shapes, full-M launches.
@@ -162,8 +190,12 @@ def run_vit(args, rank, world, device, leg="vit"):
                    "collective": "dp.OutputGatherer: all_gather_into_tensor(outputs)" if world > 1 else "none"},
         "dtype": "bf16",
         "_dt": dt,
+        "_dump": dump,
     }
     if rank == 0:
+        res["model_tflops"] = round(flops_img * B * args.steps / dt / 1e12, 1)
+        res["model_frac_of_peak"] = round(res["model_tflops"] / PEAK_BF16_TFLOPS, 4)
+    if rank == 0 and args.full:
         kern = summarize_launches(log)
         lin = kern["linear_bf16"]
         ach = lin["work"] / lin["ms"] / 1e9  # flop / ms -> TFLOP/s
@@ -189,8 +221,6 @@ def run_vit(args, rank, world, device, leg="vit"):
                                    f"python bench.py --workload {leg}` = profiles/r03/bench_{leg}_one_stream_kernel_stats.csv; of the "
                                    f"default two-stream run = profiles/r03/bench_{leg}_default_kernel_stats.csv)"}
         res["kernels"] = {k: {"launches": v["n"], "total_ms": round(v["ms"], 3)} for k, v in kern.items()}
-        res["model_tflops"] = round(flops_img * B * args.steps / dt / 1e12, 1)
-        res["model_frac_of_peak"] = round(res["model_tflops"] / PEAK_BF16_TFLOPS, 4)
     return res
 
 
@@ -207,8 +237,10 @@ def run_stub(args, rank, world, device):
     def step():
         out = torch.stack([x.sum(1), x[:, 0] * 2], 1)
         last["out"] = gather(out) if gather is not None else out
+        return last["out"]
 
-    dt = timed_steps(step, args, world)
+    dt, out = timed_steps(step, args, world)
+    dump = {"stub_out": out.float().cpu().numpy()} if args.dump_outputs and rank == 0 else {}
     dt = max_over_ranks(dt, world, device)
     want = torch.cat([torch.stack([(torch.arange(B * 4, dtype=torch.float32).view(B, 4) + 1000.0 * r).sum(1),
                                    (torch.arange(B * 4, dtype=torch.float32).view(B, 4) + 1000.0 * r)[:, 0] * 2], 1)
@@ -217,7 +249,7 @@ def run_stub(args, rank, world, device):
             "ms_per_step": round(1e3 * dt / args.steps, 3),
             "config": {"workload": "stub (CPU stand-in step, no HIP)", "per_gpu_batch": B, "global_batch": B * world,
                        "parallelism": f"dp{world}", "collective": "dp.OutputGatherer" if world > 1 else "none"},
-            "dtype": "f32", "gather_ok": bool(torch.equal(last["out"], want)), "_dt": dt}
+            "dtype": "f32", "gather_ok": bool(torch.equal(last["out"], want)), "_dt": dt, "_dump": dump}
 
 
 def summarize_launches(log):
@@ -266,6 +298,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="both", choices=["both", "vit", "whisper", "c4", "c5", "stub"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (0 = the BASELINE config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the Whisper-base leg of --workload both, per-kernel / "
+                         "roofline passes, CPU baselines, the exact-mode extra (all outside the timed region)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned at its last timed step as DIR/<leg>_<what>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact", action="store_true", help="whisper: skip the labelled exact-mode extra (generate(exact=True))")
     ap.add_argument("--whisper-layers", type=int, default=0,
@@ -277,6 +314,8 @@ def main():
     ap.add_argument("--decode-path", default="auto", choices=["auto", "launches", "persistent"],
                     help="whisper: force the per-stage launch list or the persistent layer kernel of the decode step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -312,29 +351,33 @@ def main():
         legs["vit"] = run_vit(args, rank, world, device)
     if args.workload == "c5":
         legs["c5"] = run_vit(args, rank, world, device, "c5")
-    if args.workload in ("both", "whisper", "c4"):
+    if args.workload in ("whisper", "c4") or (args.workload == "both" and args.full):
         from bench_whisper import run_whisper
 
         wleg = "c4" if args.workload == "c4" else "whisper"
         legs[wleg] = run_whisper(args, rank, world, device, sync, max_over_ranks, summarize_launches, timed_steps, leg=wleg)
 
     if rank == 0:
-        want_cpu = not args.no_cpu_baseline and world == 1  # rank 0, N = 1 only
+        want_cpu = args.full and not args.no_cpu_baseline and world == 1  # rank 0, N = 1 only
         if want_cpu and "vit" in legs:
             legs["vit"]["cpu_baseline"] = cpu_baseline_vit()
         if want_cpu and "whisper" in legs and legs["whisper"]["_layers"] == 8 and "large" not in legs["whisper"]["metric"]:  # the CPU leg is the BASELINE geometry's
             from bench_whisper import cpu_baseline_whisper
 
             legs["whisper"].update(cpu_baseline_whisper(host_cores()))
+        dump = {}
         for leg in legs.values():
             leg.pop("_dt", None)
             leg.pop("_layers", None)
+            dump.update(leg.pop("_dump", {}))
+        if args.dump_outputs:
+            dump_outputs(dump, args.dump_outputs)
         first = next(iter(legs.values()))
         res = dict(first)
+        if args.workload == "both":
+            res["metric"] = BOTH_METRIC
         if "whisper" in legs and "vit" in legs:
             w = legs["whisper"]
-            res["metric"] = ("ViT-B/16 images/s & Whisper-base audio-sec/s (BASELINE.json metric; value / unit / ms_per_step = the "
-                             "ViT-B/16 leg of configs[1], the Whisper-base leg of configs[2] is the \"whisper\" object)")
             res["config"] = dict(first["config"], legs={k: {"workload": v["config"]["workload"], "value": v["value"], "unit": v["unit"],
                                                              "ms_per_step": v["ms_per_step"]} for k, v in legs.items()})
             res["roofline"] = dict(first["roofline"], whisper=w.get("roofline"))

@@ -134,10 +134,11 @@ def run_whisper(args, rank, world, device, sync, max_over_ranks, summarize_launc
             toks = dec.run(graph=use_graph)
             return gather(toks) if gather is not None else toks
 
-        dt = timed_steps(step, args, world)
+        dt, toks = timed_steps(step, args, world)
+        dump = {f"{leg}_ids": toks.double().cpu().numpy()} if args.dump_outputs and rank == 0 else {}
         log = None
         t_decode = None
-        if rank == 0:  # outside the timed region: per-kernel event timing of the eager (front end + encoder) launches ...
+        if rank == 0 and args.full:  # outside the timed region: per-kernel event timing of the eager (front end + encoder) launches ...
             from pytorch_models import transformer as _tf
 
             _tf.ENCODER_STREAMS = 1  # per-kernel durations need non-overlapping kernels (bench.py, run_vit)
@@ -174,8 +175,9 @@ def run_whisper(args, rank, world, device, sync, max_over_ranks, summarize_launc
         "dtype": "bf16 weights and encoder activations, f32 decoder activations",
         "_dt": dt,
         "_layers": n_layers,
+        "_dump": dump,
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         kern = summarize_launches(log)
         res["kernels"] = {k: {"launches": v["n"], "total_ms": round(v["ms"], 3)} for k, v in kern.items()}
         S, d = memory.shape[1], memory.shape[2]

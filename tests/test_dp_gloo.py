@@ -99,6 +99,16 @@ def test_bench_py_single_rank_line():
     assert res["n_gpus"] == 1 and res["config"]["collective"] == "none" and res["gather_ok"] is True
 
 
+def test_bench_py_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the timed path returned at its last step (after the gather) as DIR/<name>.npy."""
+    import numpy as np
+
+    _run_bench(["--gpus", "2", "--batch", "5", "--dump-outputs", str(tmp_path)])
+    got = np.load(tmp_path / "stub_out.npy")
+    x = np.concatenate([np.arange(20, dtype=np.float32).reshape(5, 4) + 1000.0 * r for r in range(2)])
+    assert got.dtype == np.float32 and np.array_equal(got, np.stack([x.sum(1), x[:, 0] * 2], 1))
+
+
 def _gatherer_worker(rank, world, port, n, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -1,7 +1,7 @@
 """Turn two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over a bench.py run into per-launch HBM traffic of one kernel.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
     python tools/collect_traffic.py out/f out/w linear_bf16 profiles/r01/vit_traffic.json
 
 Units and gfx950 correction per /opt/skills/guides/MI355X_MICROARCH.md (HBM section): both counters are in KiB;

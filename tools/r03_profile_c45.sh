@@ -7,9 +7,9 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for w in c5 c4; do
   steps=10; warm=3; [ $w == c4 ] && steps=3 && warm=1
   echo "bench line $w"
-  timeout -k 5 500 python3 bench.py --workload $w --steps $steps --warmup $warm --no-cpu-baseline --no-exact > $out/bench_${w}_line.json 2> $out/bench_${w}.err || echo "bench $w failed"
+  timeout -k 5 500 python3 bench.py --full --workload $w --steps $steps --warmup $warm --no-cpu-baseline --no-exact > $out/bench_${w}_line.json 2> $out/bench_${w}.err || echo "bench $w failed"
   echo "kernel trace $w"
-  timeout -k 5 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$w -- python3 bench.py --workload $w --steps $steps --warmup $warm --no-cpu-baseline --no-exact > $out/kt_$w.log 2>&1 || echo "kernel trace $w failed"
+  timeout -k 5 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$w -- python3 bench.py --full --workload $w --steps $steps --warmup $warm --no-cpu-baseline --no-exact > $out/kt_$w.log 2>&1 || echo "kernel trace $w failed"
   cp $(find $out/kt_$w -name "*kernel_stats.csv" | head -1) $out/bench_${w}_kernel_stats.csv 2>/dev/null
   grep "^{\"metric\"" $out/kt_$w.log | tail -1 > $out/bench_${w}_line_under_rocprof.json
 done

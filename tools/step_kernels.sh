@@ -4,7 +4,7 @@
 out=$1; wl=$2; rows=${3:-8}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 5 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --workload $wl --no-exact --no-cpu-baseline --steps 2 --warmup 1 > $out/line.json 2>/dev/null
+timeout -k 5 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --full --workload $wl --no-exact --no-cpu-baseline --steps 2 --warmup 1 > $out/line.json 2>/dev/null
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 rm -rf $out/prof
 python3 - $out/kernel_stats.csv $rows <<'P'
