@@ -377,6 +377,34 @@ int pm_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_tile
                       int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot, float* margin_out, const void* emb,
                       const float* pos, float* x, int64_t d, int64_t V, int32_t* ticket, int64_t B, void* stream);
 
+/* ConvNeXt (reference: pytorch_models/image/convnext.py), csrc/convnext.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype
+ * PM_BF16 or PM_F32; gamma / beta / bias f32.  The pointwise MLP and the downsample's Conv2d(C, 2C, 2, 2) run on the GEMMs above.
+ *
+ * pm_dwconv7_ln: y = LayerNorm_C(Conv2d(C, C, 7, padding 3, groups C)(x) + bias) (convnext.py:22-25).  x: (N, H, W, C)
+ * contiguous; w: f32 (7, 7, C) (the weight (C, 1, 7, 7) permuted); y: (N*H*W, ldy) rows whose columns C .. ldy-1 are written as
+ * zeros (ldy = C rounded up to 64 feeds pm_linear_bf16, K % 64 == 0).  C % 4 == 0, C <= 4096, ldy % 4 == 0, 16-byte aligned
+ * f32 / 8-byte aligned bf16 operands. */
+int pm_dwconv7_ln(const void* x, int x_dtype, const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                  void* y, int64_t ldy, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, void* stream);
+
+/* pm_ln_space_to_depth: LayerNorm_C of every pixel of x (N, H, W, C) (pixel row stride ldx), then output row (n, i, j) of y
+ * (N*H/2*W/2, ldy) = the normalised pixels (2i, 2j), (2i, 2j+1), (2i+1, 2j), (2i+1, 2j+1) side by side, columns 4C .. ldy-1
+ * zero: the downsample's LayerNorm + Conv2d(C, 2C, 2, 2) (convnext.py:47-52) becomes one GEMM with the weight permuted to
+ * (Cout, kh, kw, Cin).  H, W even; any C. */
+int pm_ln_space_to_depth(const void* x, int64_t ldx, int x_dtype, const float* gamma, const float* beta, float eps, void* y,
+                         int64_t ldy, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, void* stream);
+
+/* pm_convnext_stem: Conv2d(3, d, 4, stride 4) + bias, then LayerNorm_d (convnext.py:41).  imgs: f32 NCHW (N, 3, Himg, Wimg);
+ * wt: f32 (48, d), the weight (d, 3, 4, 4) flattened to (d, 48) and transposed; y: (N*(Himg/4)*(Wimg/4), ldy) NHWC rows, columns
+ * d .. ldy-1 zero.  fp32 fma in (ci, kh, kw) order on the VALU.  d <= 384. */
+int pm_convnext_stem(const float* imgs, const float* wt, const float* bias, const float* gamma, const float* beta, float eps,
+                     void* y, int64_t ldy, int y_dtype, int64_t N, int64_t Himg, int64_t Wimg, int64_t d, void* stream);
+
+/* pm_mean_ln: y[n, :] = LayerNorm_C(mean over r < HW of x[n*HW + r, :]) (convnext.py:67-68: pool + norm); x rows with stride
+ * ldx, y (N, C) contiguous.  C <= 16000. */
+int pm_mean_ln(const void* x, int64_t ldx, int x_dtype, const float* gamma, const float* beta, float eps, void* y, int y_dtype,
+               int64_t N, int64_t HW, int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,10 @@ SIGNATURES = {
     "pm_attention_generic_bf16": ([_p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _l, _l, _l, _l, _l, _i, _p, _l, _l, _l, _p], c_int),
     "pm_vit_tokens": ([_p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
     "pm_vit_tokens_generic": ([_p, _p, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_dwconv7_ln": ([_p, _i, _p, _p, _p, _p, _f, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_ln_space_to_depth": ([_p, _l, _i, _p, _p, _f, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_convnext_stem": ([_p, _p, _p, _p, _p, _f, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_mean_ln": ([_p, _l, _i, _p, _p, _f, _p, _i, _l, _l, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

@@ -697,3 +697,85 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
                                     sup.numel(), blk.data_ptr() if blk.numel() else None, blk.numel(), B, _stream())
     check(rc, f"pm_dec_whisper_rules(B={B}, V={V})")
     return logits
+
+
+# ------------------------------------------------------------------------------------------------ ConvNeXt (csrc/convnext.hip)
+def _f32vec(t: Tensor, n: int, what: str) -> None:
+    _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, f"{what} must be f32 ({n})")
+
+
+def dwconv7_ln(x: Tensor, w: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: torch.dtype,
+               ldy: int | None = None) -> Tensor:
+    """pm_dwconv7_ln: x (N, H, W, C) bf16 | f32 contiguous, w f32 (7, 7, C) -> LayerNorm_C(dwconv7x7(x) + bias) as
+    (N*H*W, ldy) rows of out_dtype, columns C .. ldy-1 zero (ldy defaults to C rounded up to 64)."""
+    _cuda(x, w, bias, gamma, beta)
+    _need(x.dim() == 4 and x.is_contiguous(), "dwconv7_ln: x must be contiguous (N, H, W, C)")
+    N, H, W, C = x.shape
+    _need(w.shape == (7, 7, C) and w.dtype == torch.float32 and w.is_contiguous(), "dwconv7_ln: w must be f32 (7, 7, C)")
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _f32vec(t, C, f"dwconv7_ln: {nm}")
+    ldy = ldy if ldy is not None else -(-C // 64) * 64
+    out = torch.empty((N * H * W, ldy), dtype=out_dtype, device=x.device)
+    nbytes = float(x.numel() * x.element_size() + out.numel() * out.element_size())
+    rc = _launch("dwconv7_ln", (98.0 * x.numel(), nbytes), lambda: lib().pm_dwconv7_ln(
+        x.data_ptr(), _dt(x), w.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), ldy,
+        _dt(out), N, H, W, C, _stream()))
+    check(rc, f"pm_dwconv7_ln(N={N}, H={H}, W={W}, C={C})")
+    return out
+
+
+def ln_space_to_depth(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: torch.dtype, ldy: int | None = None) -> Tensor:
+    """pm_ln_space_to_depth: x (N, H, W, C) -> (N*H/2*W/2, ldy) rows [LN(x[2i, 2j]), LN(x[2i, 2j+1]), LN(x[2i+1, 2j]),
+    LN(x[2i+1, 2j+1]), 0 ...] (ldy defaults to 4C rounded up to 64)."""
+    _cuda(x, gamma, beta)
+    _need(x.dim() == 4 and x.stride(3) == 1 and x.stride(2) >= x.shape[3] and x.stride(1) == x.shape[2] * x.stride(2)
+          and x.stride(0) == x.shape[1] * x.stride(1), "ln_space_to_depth: x must be (N, H, W, C) pixel rows")
+    N, H, W, C = x.shape
+    _need(H % 2 == 0 and W % 2 == 0, f"ln_space_to_depth: even sides needed, got {H} x {W}")
+    _f32vec(gamma, C, "ln_space_to_depth: gamma")
+    _f32vec(beta, C, "ln_space_to_depth: beta")
+    ldy = ldy if ldy is not None else -(-4 * C // 64) * 64
+    out = torch.empty((N * (H // 2) * (W // 2), ldy), dtype=out_dtype, device=x.device)
+    nbytes = float(x.numel() * x.element_size() + out.numel() * out.element_size())
+    rc = _launch("ln_space_to_depth", (0.0, nbytes), lambda: lib().pm_ln_space_to_depth(
+        x.data_ptr(), x.stride(2), _dt(x), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), ldy, _dt(out), N, H, W, C,
+        _stream()))
+    check(rc, f"pm_ln_space_to_depth(N={N}, H={H}, W={W}, C={C})")
+    return out
+
+
+def convnext_stem(imgs: Tensor, wt: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, eps: float,
+                  out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """pm_convnext_stem: imgs f32 (N, 3, H, W), wt f32 (48, d) -> LayerNorm_d(Conv2d(3, d, 4, 4)(imgs) + bias) as NHWC
+    (N, H/4, W/4, d) of out_dtype."""
+    _cuda(imgs, wt, bias, gamma, beta)
+    _need(imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.dtype == torch.float32 and imgs.is_contiguous(),
+          "convnext_stem: imgs must be contiguous f32 (N, 3, H, W)")
+    d = wt.shape[1]
+    _need(wt.shape == (48, d) and wt.dtype == torch.float32 and wt.is_contiguous(), "convnext_stem: wt must be f32 (48, d)")
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _f32vec(t, d, f"convnext_stem: {nm}")
+    N, _, H, W = imgs.shape
+    out = torch.empty((N, H // 4, W // 4, d), dtype=out_dtype, device=imgs.device)
+    flops = 2.0 * 48 * d * out.numel() / d
+    nbytes = float(imgs.numel() * 4 + out.numel() * out.element_size())
+    rc = _launch("convnext_stem", (flops, nbytes), lambda: lib().pm_convnext_stem(
+        imgs.data_ptr(), wt.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), d,
+        _dt(out), N, H, W, d, _stream()))
+    check(rc, f"pm_convnext_stem(N={N}, H={H}, W={W}, d={d})")
+    return out
+
+
+def mean_ln(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: torch.dtype) -> Tensor:
+    """pm_mean_ln: x (N, HW, C) rows (unit channel stride) -> (N, C) = LayerNorm_C(mean over the HW rows)."""
+    _cuda(x, gamma, beta)
+    _need(x.dim() == 3 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1), "mean_ln: x must be (N, HW, C) rows")
+    N, HW, C = x.shape
+    _f32vec(gamma, C, "mean_ln: gamma")
+    _f32vec(beta, C, "mean_ln: beta")
+    out = torch.empty((N, C), dtype=out_dtype, device=x.device)
+    rc = _launch("mean_ln", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_mean_ln(
+        x.data_ptr(), x.stride(1), _dt(x), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), _dt(out), N, HW, C,
+        _stream()))
+    check(rc, f"pm_mean_ln(N={N}, HW={HW}, C={C})")
+    return out
