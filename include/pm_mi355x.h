@@ -405,6 +405,49 @@ int pm_convnext_stem(const float* imgs, const float* wt, const float* bias, cons
 int pm_mean_ln(const void* x, int64_t ldx, int x_dtype, const float* gamma, const float* beta, float eps, void* y, int y_dtype,
                int64_t N, int64_t HW, int64_t C, void* stream);
 
+/* MaxViT (reference: pytorch_models/image/maxvit.py), csrc/maxvit.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype PM_BF16 or
+ * PM_F32.  The 1 x 1 convolutions (BatchNorms folded), q/k/v / out projections and the MLPs run on the GEMMs above.
+ *
+ * pm_window_attention_bf16: softmax(q k^T / sqrt(32) + bias[h]) v per (window, head), head dim 32, over the windows of an NHWC
+ * image (N, Himg, Wimg) whose pixel rows hold the heads side by side: q / k / v of head h at pixel row r are the 32 bf16 at
+ * base + r*ld + h*32 (the packed QKV projection read in place), the output goes to o + r*ldo + h*32 (pixel order, heads merged).
+ * mode 0 = block (maxvit.py:70-81, block/unblock): window (n, wy, wx), token (i, j) is pixel (wy*ws + i, wx*ws + j); mode 1 =
+ * grid (maxvit.py:84-91, grid/ungrid): pixel (i*Himg/ws + wy, j*Wimg/ws + wx).  Token t = i*ws + j indexes bias, f32 (H, L, L)
+ * with L = ws*ws <= 64 (RelativeMHA's gathered relative bias, maxvit.py:105-112, shared by every window), or null.  bf16 MFMA,
+ * fp32 softmax.  Himg, Wimg multiples of ws; ld % 8 == 0, 16-byte aligned q / k / v. */
+int pm_window_attention_bf16(const void* q, const void* k, const void* v, int64_t ld, void* o, int64_t ldo, const float* bias,
+                             int64_t N, int64_t Himg, int64_t Wimg, int64_t n_heads, int64_t ws, int mode, void* stream);
+
+/* pm_dwconv3_bn_act: y = gelu_tanh(Conv2d(C, C, 3, stride, groups C)(x) * scale + shift) [* gate[n, c]] (MBConv's depthwise
+ * conv_norm_act, maxvit.py:27-31 / 52, with its BatchNorm folded to scale / shift, and the squeeze-excitation product of
+ * maxvit.py:44).  stride 1: padding 1; stride 2: the reference's F.pad(x, (0, 1, 0, 1)) + padding 0 (maxvit.py:19-21), output
+ * ((H - 2) / 2 + 1, (W - 2) / 2 + 1).  x (N, H, W, C) contiguous; w f32 (3, 3, C); gate f32 (N, C) or null; psum, if not null,
+ * receives f32 (N, Ho, C): the sums over each output row of the UNGATED output (the squeeze-excitation's pool, in a fixed order);
+ * y may be null when psum is not.  C % 4 == 0. */
+int pm_dwconv3_bn_act(const void* x, int x_dtype, const float* w, const float* scale, const float* shift, const float* gate,
+                      float* psum, void* y, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, int stride, void* stream);
+
+/* pm_se_gate: gate[n, :] = sigmoid(w2 @ silu(w1 @ m + b1) + b2) with m = (sum over t < ntiles of psum[n, t, :]) / hw
+ * (SqueezeExcitation, maxvit.py:34-41).  psum f32 (N, ntiles, C); w1 f32 (R, C); w2 f32 (C, R); gate f32 (N, C).  fp32. */
+int pm_se_gate(const float* psum, int64_t ntiles, int64_t hw, const float* w1, const float* b1, const float* w2, const float* b2,
+               float* gate, int64_t N, int64_t C, int64_t R, void* stream);
+
+/* pm_maxvit_stem: gelu_tanh(Conv2d(3, d, 3, 2, bias=False)(F.pad(imgs, (0, 1, 0, 1))) * bn_scale + bn_shift) (maxvit.py:150-152).
+ * imgs f32 NCHW (N, 3, Himg, Wimg); wt f32 (27, d), the weight (d, 3, 3, 3) times the BatchNorm scale, flattened to (d, 27) and
+ * transposed; shift f32 (d); y (N*Ho*Wo, ldy) NHWC rows, columns d .. ldy-1 zero.  fp32 fma on the VALU.  d <= 256. */
+int pm_maxvit_stem(const float* imgs, const float* wt, const float* shift, void* y, int64_t ldy, int y_dtype, int64_t N,
+                   int64_t Himg, int64_t Wimg, int64_t d, void* stream);
+
+/* pm_im2col3x3_nhwc: y[(n, h, w), (kh*3 + kw)*C + c] = x[n, h + kh - 1, w + kw - 1, c] (zero outside), columns 9C .. ldy-1 zero:
+ * the stem's second Conv2d(s, s, 3) (maxvit.py:154) as one GEMM with the weight permuted to (Cout, kh, kw, Cin).  x (N, H, W, C)
+ * contiguous; C % 4 == 0, ldy % 4 == 0. */
+int pm_im2col3x3_nhwc(const void* x, int x_dtype, void* y, int64_t ldy, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C,
+                      void* stream);
+
+/* pm_avgpool2x2_nhwc: y (N, H/2, W/2, C) = AvgPool2d(2)(x) (the MBConv shortcut, maxvit.py:59-60); x (N, H, W, C) contiguous;
+ * H, W even, C % 4 == 0. */
+int pm_avgpool2x2_nhwc(const void* x, int x_dtype, void* y, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ SIGNATURES = {
     "pm_ln_space_to_depth": ([_p, _l, _i, _p, _p, _f, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
     "pm_convnext_stem": ([_p, _p, _p, _p, _p, _f, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
     "pm_mean_ln": ([_p, _l, _i, _p, _p, _f, _p, _i, _l, _l, _l, _p], c_int),
+    "pm_window_attention_bf16": ([_p, _p, _p, _l, _p, _l, _p, _l, _l, _l, _l, _l, _i, _p], c_int),
+    "pm_dwconv3_bn_act": ([_p, _i, _p, _p, _p, _p, _p, _p, _i, _l, _l, _l, _l, _i, _p], c_int),
+    "pm_se_gate": ([_p, _l, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_maxvit_stem": ([_p, _p, _p, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_im2col3x3_nhwc": ([_p, _i, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_avgpool2x2_nhwc": ([_p, _i, _p, _i, _l, _l, _l, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

@@ -779,3 +779,127 @@ def mean_ln(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: torch
         _stream()))
     check(rc, f"pm_mean_ln(N={N}, HW={HW}, C={C})")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MaxViT (csrc/maxvit.hip)
+WINDOW_MODES = dict(block=0, grid=1)
+
+
+def window_attention(q: Tensor, k: Tensor, v: Tensor, N: int, H: int, W: int, n_heads: int, ws: int, mode: str,
+                     bias: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """pm_window_attention_bf16: q / k / v bf16 (N*H*W, >= 32*n_heads) pixel rows sharing one row stride (column slices of the packed
+    QKV projection), head h in columns 32h .. 32h+31 -> (N*H*W, 32*n_heads) bf16, softmax(q k^T / sqrt(32) + bias[h]) v over the
+    ws x ws windows of ``mode`` 'block' or 'grid'; bias f32 (n_heads, ws*ws, ws*ws) or None."""
+    _cuda(q, k, v, bias, out)
+    M, D = N * H * W, 32 * n_heads
+    for t in (q, k, v):
+        _need(t.dim() == 2 and t.dtype == torch.bfloat16 and t.shape[0] == M and t.shape[1] >= D and t.stride(1) == 1,
+              f"window_attention: q / k / v must be bf16 ({M}, >= {D}) rows")
+    _need(q.stride(0) == k.stride(0) == v.stride(0), "window_attention: q / k / v share one row stride")
+    _need(mode in WINDOW_MODES, f"window_attention: mode must be 'block' or 'grid', got {mode!r}")
+    L = ws * ws
+    if bias is not None:
+        _need(bias.dtype == torch.float32 and bias.shape == (n_heads, L, L) and bias.is_contiguous(),
+              f"window_attention: bias must be contiguous f32 ({n_heads}, {L}, {L})")
+    if out is None:
+        out = torch.empty((M, D), dtype=torch.bfloat16, device=q.device)
+    _need(out.dtype == torch.bfloat16 and out.shape[0] == M and out.shape[1] >= D and out.stride(1) == 1, "window_attention: bad out")
+    nbytes = float(M * D * 2 * 4)
+    rc = _launch("window_attention", (4.0 * M * L * D, nbytes), lambda: lib().pm_window_attention_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0),
+        bias.data_ptr() if bias is not None else None, N, H, W, n_heads, ws, WINDOW_MODES[mode], _stream()))
+    check(rc, f"pm_window_attention_bf16(N={N}, H={H}, W={W}, heads={n_heads}, ws={ws}, mode={mode})")
+    return out
+
+
+def dwconv3_bn_act(x: Tensor, w: Tensor, scale: Tensor, shift: Tensor, stride: int, *, gate: Tensor | None = None,
+                   out_dtype: torch.dtype | None = None, want_psum: bool = False, write_y: bool = True):
+    """pm_dwconv3_bn_act: x (N, H, W, C) bf16 | f32 contiguous, w f32 (3, 3, C) -> gelu_tanh(dwconv3x3(x) * scale + shift) [* gate]
+    as (N, Ho, Wo, C) of out_dtype (stride 2: the reference's right / bottom zero pad).  want_psum: also (or, with write_y=False,
+    only) the f32 (N, Ho, C) per-row channel sums of the ungated output.  Returns y, psum, or (y, psum)."""
+    _cuda(x, w, scale, shift, gate)
+    _need(x.dim() == 4 and x.is_contiguous(), "dwconv3_bn_act: x must be contiguous (N, H, W, C)")
+    _need(stride in (1, 2), "dwconv3_bn_act: stride 1 or 2")
+    N, H, W, C = x.shape
+    _need(w.shape == (3, 3, C) and w.dtype == torch.float32 and w.is_contiguous(), "dwconv3_bn_act: w must be f32 (3, 3, C)")
+    _f32vec(scale, C, "dwconv3_bn_act: scale")
+    _f32vec(shift, C, "dwconv3_bn_act: shift")
+    if gate is not None:
+        _need(gate.dtype == torch.float32 and gate.shape == (N, C) and gate.is_contiguous(), "dwconv3_bn_act: gate must be f32 (N, C)")
+    _need(write_y or want_psum, "dwconv3_bn_act: nothing to compute")
+    Ho, Wo = (H, W) if stride == 1 else ((H - 2) // 2 + 1, (W - 2) // 2 + 1)
+    y = torch.empty((N, Ho, Wo, C), dtype=out_dtype or x.dtype, device=x.device) if write_y else None
+    ps = torch.empty((N, Ho, C), dtype=torch.float32, device=x.device) if want_psum else None
+    nbytes = float(x.numel() * x.element_size() + (y.numel() * y.element_size() if y is not None else 0))
+    rc = _launch("dwconv3_bn_act", (18.0 * N * Ho * Wo * C, nbytes), lambda: lib().pm_dwconv3_bn_act(
+        x.data_ptr(), _dt(x), w.data_ptr(), scale.data_ptr(), shift.data_ptr(), gate.data_ptr() if gate is not None else None,
+        ps.data_ptr() if ps is not None else None, y.data_ptr() if y is not None else None, _dt(y) if y is not None else PM_F32,
+        N, H, W, C, stride, _stream()))
+    check(rc, f"pm_dwconv3_bn_act(N={N}, H={H}, W={W}, C={C}, stride={stride})")
+    if write_y and want_psum:
+        return y, ps
+    return y if write_y else ps
+
+
+def se_gate(psum: Tensor, hw: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Tensor:
+    """pm_se_gate: psum f32 (N, T, C) partial sums over hw pixels, w1 f32 (R, C), w2 f32 (C, R) -> gate f32 (N, C) =
+    sigmoid(w2 @ silu(w1 @ mean + b1) + b2)."""
+    _cuda(psum, w1, b1, w2, b2)
+    _need(psum.dim() == 3 and psum.dtype == torch.float32 and psum.is_contiguous(), "se_gate: psum must be contiguous f32 (N, T, C)")
+    N, T, C = psum.shape
+    R = w1.shape[0]
+    _need(w1.shape == (R, C) and w2.shape == (C, R) and w1.dtype == w2.dtype == torch.float32 and w1.is_contiguous()
+          and w2.is_contiguous(), "se_gate: w1 f32 (R, C), w2 f32 (C, R)")
+    _f32vec(b1, R, "se_gate: b1")
+    _f32vec(b2, C, "se_gate: b2")
+    gate = torch.empty((N, C), dtype=torch.float32, device=psum.device)
+    rc = _launch("se_gate", (4.0 * N * C * R, float(psum.numel() * 4)), lambda: lib().pm_se_gate(
+        psum.data_ptr(), T, hw, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), gate.data_ptr(), N, C, R, _stream()))
+    check(rc, f"pm_se_gate(N={N}, T={T}, C={C}, R={R})")
+    return gate
+
+
+def maxvit_stem(imgs: Tensor, wt: Tensor, shift: Tensor, out_dtype: torch.dtype = torch.float32, ldy: int | None = None) -> Tensor:
+    """pm_maxvit_stem: imgs f32 (N, 3, H, W), wt f32 (27, d) (BatchNorm scale folded) -> gelu_tanh(conv3x3/2(imgs) + shift) as
+    (N, Ho, Wo, ldy) NHWC rows of out_dtype (columns d .. ldy-1 zero)."""
+    _cuda(imgs, wt, shift)
+    _need(imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.dtype == torch.float32 and imgs.is_contiguous(),
+          "maxvit_stem: imgs must be contiguous f32 (N, 3, H, W)")
+    d = wt.shape[1]
+    _need(wt.shape == (27, d) and wt.dtype == torch.float32 and wt.is_contiguous(), "maxvit_stem: wt must be f32 (27, d)")
+    _f32vec(shift, d, "maxvit_stem: shift")
+    N, _, H, W = imgs.shape
+    Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    ldy = ldy or d
+    out = torch.empty((N, Ho, Wo, ldy), dtype=out_dtype, device=imgs.device)
+    rc = _launch("maxvit_stem", (54.0 * N * Ho * Wo * d, float(imgs.numel() * 4 + out.numel() * out.element_size())),
+                 lambda: lib().pm_maxvit_stem(imgs.data_ptr(), wt.data_ptr(), shift.data_ptr(), out.data_ptr(), ldy, _dt(out), N, H, W,
+                                              d, _stream()))
+    check(rc, f"pm_maxvit_stem(N={N}, H={H}, W={W}, d={d})")
+    return out
+
+
+def im2col3x3(x: Tensor, out_dtype: torch.dtype | None = None, ldy: int | None = None) -> Tensor:
+    """pm_im2col3x3_nhwc: x (N, H, W, C) contiguous -> (N*H*W, ldy) rows of pad-1 3 x 3 patches in (kh, kw, C) order, zero past
+    9C (ldy defaults to 9C rounded up to 64)."""
+    _cuda(x)
+    _need(x.dim() == 4 and x.is_contiguous(), "im2col3x3: x must be contiguous (N, H, W, C)")
+    N, H, W, C = x.shape
+    ldy = ldy if ldy is not None else -(-9 * C // 64) * 64
+    out = torch.empty((N * H * W, ldy), dtype=out_dtype or x.dtype, device=x.device)
+    rc = _launch("im2col3x3", (0.0, float(x.numel() * x.element_size() + out.numel() * out.element_size())), lambda: lib().pm_im2col3x3_nhwc(
+        x.data_ptr(), _dt(x), out.data_ptr(), ldy, _dt(out), N, H, W, C, _stream()))
+    check(rc, f"pm_im2col3x3_nhwc(N={N}, H={H}, W={W}, C={C}, ldy={ldy})")
+    return out
+
+
+def avgpool2x2(x: Tensor, out_dtype: torch.dtype | None = None) -> Tensor:
+    """pm_avgpool2x2_nhwc: x (N, H, W, C) contiguous -> (N, H/2, W/2, C) 2 x 2 means."""
+    _cuda(x)
+    _need(x.dim() == 4 and x.is_contiguous(), "avgpool2x2: x must be contiguous (N, H, W, C)")
+    N, H, W, C = x.shape
+    out = torch.empty((N, H // 2, W // 2, C), dtype=out_dtype or x.dtype, device=x.device)
+    rc = _launch("avgpool2x2", (0.0, float(x.numel() * x.element_size() + out.numel() * out.element_size())), lambda: lib().pm_avgpool2x2_nhwc(
+        x.data_ptr(), _dt(x), out.data_ptr(), _dt(out), N, H, W, C, _stream()))
+    check(rc, f"pm_avgpool2x2_nhwc(N={N}, H={H}, W={W}, C={C})")
+    return out

@@ -1,3 +1,4 @@
 from .convnext import ConvNeXt
+from .maxvit import MaxViT
 from .mobile_vit import MobileViT
 from .vit import ViT
