@@ -163,7 +163,9 @@ int pm_attention_bf16(const void* q, int64_t q_stride_b, int64_t q_stride_t,
 
 /* pm_attention_bf16 with the additive attn_mask of transformer.py:52 (`attn_bias`: T5 / MaxViT style relative position
  * bias): scores + bias[b, h, i, j] before the softmax.  bias: f32, addressed bias + b*stride_b + h*stride_h + i*stride_q + j
- * (stride 0 = broadcast over batch / heads); -inf entries mask keys (a fully masked row yields NaN, like torch). */
+ * (stride 0 = broadcast over batch / heads); -inf entries mask keys.  A query row with no visible key (every bias entry -inf,
+ * or left padding under causal) yields ZEROS, as F.scaled_dot_product_attention does on the CPU - never NaN, and never an
+ * average over hidden keys.  The same holds for pm_attention_generic_* and pm_window_attention_bf16. */
 int pm_attention_bias_bf16(const void* q, int64_t q_stride_b, int64_t q_stride_t,
                            const void* k, int64_t k_stride_b, int64_t k_stride_t,
                            const void* v, int64_t v_stride_b, int64_t v_stride_t,

@@ -172,7 +172,7 @@ _Pragma("unroll")                                                               
         }                                                                                                                \
         if ((MASKED) && (tail || diag)) {                                                                                \
           const int key = key_base + kb * 32 + (i & 3) + 8 * (i >> 2);                                                   \
-          if (key >= Lk || (CAUSAL && key > qi)) v = -1e30f;                                                             \
+          if (key >= Lk || (CAUSAL && key > qi)) v = BIAS ? -INFINITY : -1e30f;  /* see the dead-row note below */        \
         }                                                                                                                \
         sc[kb][i] = v;                                                                                                   \
         mx = fmaxf(mx, v);                                                                                               \
@@ -244,8 +244,13 @@ _Pragma("unroll")                                                               
   for (; t < nT; ++t) { PM_ATT_TILE(true, t & 1) }
 #undef PM_ATT_TILE
 
+  // Dead rows (BIAS only: without a bias key 0 is visible to every query, causal or not).  A row whose visible keys all carry
+  // a -inf bias returns ZEROS, as F.scaled_dot_product_attention does on the CPU and pytorch_models/_cpu.py with it.  Hidden keys
+  // (past Lk, above the causal diagonal) are -inf like the masked ones, m_run stays at its finite -1e30 start until a live key
+  // arrives, so every hidden or masked key has p = exp2(-inf) = 0 exactly and a dead row ends with l = 0 and O = 0: with the
+  // finite sentinel the hidden keys of such a row met m_run = -1e30 and took weight exp2(0) = 1.
   const float l_tot = ah_add_xor32(l_run);
-  const float inv = 1.0f / l_tot;
+  const float inv = BIAS ? (l_tot > 0.f ? 1.0f / l_tot : 0.f) : 1.0f / l_tot;
   if (qi < Lq) {
     bf16* op = O + (int64_t)b * osb + (int64_t)qi * ost + h * 64;
 #pragma unroll

@@ -146,12 +146,13 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const T* __restrict__
     mx = wave_max(mx);
     float sum = 0.f;
     for (int k = lane; k < Lk; k += 64) {
-      const float p = expf(sc[qq * GMAXK + k] - mx);
+      const float p = mx == -INFINITY ? 0.f : expf(sc[qq * GMAXK + k] - mx);  // dead row: no -inf - -inf
       sc[qq * GMAXK + k] = p;
       sum += p;
     }
     sum = wave_sum(sum);
-    if (lane == 0) inv_sum[qq] = 1.0f / sum;
+    // a row with no visible key (every score -inf) returns zeros, as F.scaled_dot_product_attention does on the CPU
+    if (lane == 0) inv_sum[qq] = sum > 0.f ? 1.0f / sum : 0.f;
   }
   __syncthreads();
   // ---- P.V: thread -> (query tid / 32, 4 dims (tid % 32) * 4); head dims that are multiples of 2 only: 2 dims per thread

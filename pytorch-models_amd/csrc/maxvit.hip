@@ -156,6 +156,7 @@ __global__ __launch_bounds__(64 * WA_WAVES) void window_attn_kernel(const bf16* 
     }
     m = fmaxf(m, __shfl_xor(m, 16, 64));
     m = fmaxf(m, __shfl_xor(m, 32, 64));
+    if (m == -INFINITY) m = 0.f;  // a bias row of -inf only: p = exp2(-inf) = 0 for every key, and the row is zeros (below)
     float sum = 0.f;
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(64 * WA_WAVES) void window_attn_kernel(const bf16* 
         pf[c][4 + j] = (bf16)s[2 * c + 1][j];
       }
     }
-    const float inv = 1.0f / sum;
+    const float inv = sum > 0.f ? 1.0f / sum : 0.f;  // dead row -> zeros, as F.scaled_dot_product_attention on the CPU
     const int64_t orow = qrow[qb];
 #pragma unroll
     for (int db = 0; db < 2; ++db) {

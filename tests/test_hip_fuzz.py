@@ -96,8 +96,7 @@ def test_attention_random_shapes(B, H, Lq, Lk, causal):
     got = ops.attention(q, k, v, H, causal, None)
     qh, kh, vh = (RT.split_heads(t.float().cpu(), H) for t in (q, k, v))
     want = RT.merge_heads(RT.sdpa(qh, kh, vh, None, causal))
-    live = torch.ones(Lq, dtype=torch.bool)
-    torch.testing.assert_close(got.float().cpu()[:, live], want[:, live], rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(got.float().cpu(), want, rtol=2e-2, atol=2e-2)  # no mask here: every row is live
 
 
 def _dec_cases(n, seed):
