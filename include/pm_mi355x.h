@@ -450,6 +450,32 @@ int pm_im2col3x3_nhwc(const void* x, int x_dtype, void* y, int64_t ldy, int y_dt
  * H, W even, C % 4 == 0. */
 int pm_avgpool2x2_nhwc(const void* x, int x_dtype, void* y, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, void* stream);
 
+/* ---- DETR (reference: pytorch_models/image/detr.py): ResNet bottleneck backbone and head-dim-32 attention.
+ * pm_conv_bf16: y = relu?(conv(x, w) + bias [+ resid]) as an implicit GEMM on the bf16 MFMA (csrc/resnet.hip) - the ReLU comes
+ * AFTER the residual add (Bottleneck.forward, detr.py:33; pm_linear_bf16's act(..) + resid cannot express that).  x: bf16 NHWC
+ * (N, H, W, Cin) contiguous; w: bf16 (Cout, ksize, ksize, Cin) contiguous (an eval BatchNorm folded in by the caller); bias: f32
+ * (Cout) or NULL; resid: bf16 like y or NULL; y: bf16 (N, Ho, Wo, Cout), Ho = (H + 2 pad - ksize) / stride + 1.  ksize 3 (pad 1)
+ * or 1 (pad 0); stride 1 or 2; Cin % 64 == 0; any Cout.  The input tile is gathered from the NHWC rows into LDS (zeros outside
+ * the image): no im2col buffer.  fp32 accumulation, one rounding to bf16.  relu: 0 | 1.  All pointers 16-byte aligned. */
+int pm_conv_bf16(const void* x, int64_t N, int64_t H, int64_t W, int64_t Cin, const void* w, const float* bias, const void* resid,
+                 void* y, int64_t Cout, int64_t ksize, int64_t stride, int relu, void* stream);
+
+/* pm_resnet_stem: MaxPool2d(3, 2, 1)(relu(Conv2d(3, 64, 7, 2, 3, bias=False)(imgs) * bn_scale + bn_shift)) (detr.py:40-45).
+ * imgs f32 NCHW (N, 3, Himg, Wimg); wt f32 (147, 64): the weight (64, 3, 7, 7) times the BatchNorm scale, flattened to (64, 147)
+ * and transposed; shift f32 (64); conv_map: caller-owned scratch, bf16 (N, Hc, Wc, 64) with Hc = (Himg - 1) / 2 + 1 (the
+ * convolution's output, written and then pooled: two kernels); y: bf16 NHWC (N, Hp, Wp, 64), Hp = (Hc - 1) / 2 + 1.  fp32 fma
+ * on the VALU (K = 147 does not suit the matrix pipe). */
+int pm_resnet_stem(const float* imgs, const float* wt, const float* shift, void* conv_map, void* y, int64_t N, int64_t Himg,
+                   int64_t Wimg, void* stream);
+
+/* pm_attention_hd32_bf16: softmax(q k^T / sqrt(32)) v for head dim 32 on the bf16 MFMA, flash style (online fp32 softmax over
+ * key tiles of 64, the key tail masked in the kernel; csrc/attention_hd32.hip).  Addressing as pm_attention_bf16 with h*32 head
+ * offsets; any Lq >= 1, Lk >= 1; no bias, no causal mask (DETR has neither: detr.py:64-87).  Strides multiples of 8 elements
+ * (o: 4), q / k / v 16-byte aligned (o: 8). */
+int pm_attention_hd32_bf16(const void* q, int64_t q_stride_b, int64_t q_stride_t, const void* k, int64_t k_stride_b,
+                           int64_t k_stride_t, const void* v, int64_t v_stride_b, int64_t v_stride_t, void* o,
+                           int64_t o_stride_b, int64_t o_stride_t, int64_t B, int64_t H, int64_t Lq, int64_t Lk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

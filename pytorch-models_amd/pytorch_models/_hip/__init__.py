@@ -79,6 +79,9 @@ SIGNATURES = {
     "pm_maxvit_stem": ([_p, _p, _p, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
     "pm_im2col3x3_nhwc": ([_p, _i, _p, _l, _i, _l, _l, _l, _l, _p], c_int),
     "pm_avgpool2x2_nhwc": ([_p, _i, _p, _i, _l, _l, _l, _l, _p], c_int),
+    "pm_conv_bf16": ([_p, _l, _l, _l, _l, _p, _p, _p, _p, _l, _l, _l, _i, _p], c_int),
+    "pm_resnet_stem": ([_p, _p, _p, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_attention_hd32_bf16": ([_p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

@@ -138,8 +138,9 @@ def _linear_bytes(x: Tensor, w: Tensor, out: Tensor, resid: Tensor | None) -> fl
 
 def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none", resid: Tensor | None = None,
            out_dtype: torch.dtype = torch.bfloat16, out: Tensor | None = None, ln_stats: Tensor | None = None,
-           ln_s: Tensor | None = None, want_row_stats: bool = False):
-    """y = act(x @ w.T + bias) + resid.  x (M, K) bf16, w (N, K) bf16, bias f32 (N), resid (M, N) bf16|f32.
+           ln_s: Tensor | None = None, want_row_stats: bool = False, resid_period: int = 0):
+    """y = act(x @ w.T + bias) + resid.  x (M, K) bf16, w (N, K) bf16, bias f32 (N), resid (M, N) bf16|f32 - or, with
+    resid_period = P > 0, (P, N): row m adds resid[m % P] (a position table broadcast over the batch).
     LayerNorm fold (pm_linear_bf16_ln): ln_stats (M, 2) + ln_s (N) normalise the input rows in the epilogue;
     want_row_stats=True additionally returns the (M, N/64, 2) partial statistics of the output rows."""
     _cuda(x, w, bias, resid, out)
@@ -154,7 +155,8 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
         out = torch.empty((M, N), dtype=out_dtype, device=x.device)
     _need(out.shape == (M, N) and out.stride(1) == 1, "linear: bad out")
     if resid is not None:
-        _need(resid.shape == (M, N) and resid.stride(1) == 1, "linear: resid must be (M, N), row-major")
+        _need(resid_period >= 0 and resid.shape == (resid_period or M, N) and resid.stride(1) == 1,
+              "linear: resid must be (M, N) - (resid_period, N) when periodic -, row-major")
     if ln_stats is not None or want_row_stats:
         _need((ln_stats is None) == (ln_s is None), "linear: ln_stats and ln_s go together")
         if ln_stats is not None:
@@ -167,8 +169,8 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
     rc = _launch("linear_bf16", (2.0 * M * N * K, _linear_bytes(x, w, out, resid)), lambda: lib().pm_linear_bf16_ws(
         x.data_ptr(), x.stride(0), 0, 0, w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
         resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0,
-        _dt(resid) if resid is not None else 0, 0, out.data_ptr(), out.stride(0), _dt(out), M, N, K, ACT[act],
-        ln_stats.data_ptr() if ln_stats is not None else None, ln_s.data_ptr() if ln_s is not None else None,
+        _dt(resid) if resid is not None else 0, resid_period if resid is not None else 0, out.data_ptr(), out.stride(0),
+        _dt(out), M, N, K, ACT[act], ln_stats.data_ptr() if ln_stats is not None else None, ln_s.data_ptr() if ln_s is not None else None,
         rows.data_ptr() if rows is not None else None, ws, ws_bytes, _stream()))
     check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
     return (out, rows) if want_row_stats else out
@@ -902,4 +904,72 @@ def avgpool2x2(x: Tensor, out_dtype: torch.dtype | None = None) -> Tensor:
     rc = _launch("avgpool2x2", (0.0, float(x.numel() * x.element_size() + out.numel() * out.element_size())), lambda: lib().pm_avgpool2x2_nhwc(
         x.data_ptr(), _dt(x), out.data_ptr(), _dt(out), N, H, W, C, _stream()))
     check(rc, f"pm_avgpool2x2_nhwc(N={N}, H={H}, W={W}, C={C})")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------- DETR
+def conv_bf16(x: Tensor, w: Tensor, bias: Tensor | None, stride: int = 1, relu: bool = False, resid: Tensor | None = None) -> Tensor:
+    """pm_conv_bf16: x (N, H, W, Cin) bf16 NHWC, w (Cout, k, k, Cin) bf16 with k = 3 (pad 1) or 1 (pad 0), bias f32 (Cout) ->
+    relu?(conv(x, w) + bias [+ resid]) as (N, Ho, Wo, Cout) bf16; the ReLU comes after the residual add.  Cin % 64 == 0."""
+    _cuda(x, w, bias, resid)
+    _need(x.dim() == 4 and w.dim() == 4 and x.is_contiguous() and w.is_contiguous(), "conv_bf16: contiguous NHWC x and (Cout, k, k, Cin) w")
+    _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "conv_bf16: bf16 operands")
+    N, H, W, Cin = x.shape
+    Cout, kh, kw, ci = w.shape
+    _need(kh == kw and kh in (1, 3), f"conv_bf16: 3 x 3 or 1 x 1 kernels, got {kh} x {kw}")
+    _need(ci == Cin and Cin % 64 == 0, f"conv_bf16: Cin must match the weight and be a multiple of 64 (x {Cin}, w {ci})")
+    _need(stride in (1, 2), "conv_bf16: stride 1 or 2")
+    _need(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout), "conv_bf16: bias must be f32 (Cout)")
+    pad = 1 if kh == 3 else 0
+    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kh) // stride + 1
+    out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
+    _need(resid is None or (resid.shape == out.shape and resid.dtype == torch.bfloat16 and resid.is_contiguous()),
+          "conv_bf16: resid must be bf16 of the output's shape")
+    rc = _launch("conv_bf16", (2.0 * N * Ho * Wo * Cout * kh * kw * Cin, float(2 * (x.numel() + w.numel() + out.numel() * (2 if resid is not None else 1)))),
+                 lambda: lib().pm_conv_bf16(x.data_ptr(), N, H, W, Cin, w.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                            resid.data_ptr() if resid is not None else None, out.data_ptr(), Cout, kh, stride,
+                                            int(relu), _stream()))
+    check(rc, f"pm_conv_bf16(N={N}, H={H}, W={W}, Cin={Cin}, Cout={Cout}, k={kh}, stride={stride})")
+    return out
+
+
+def resnet_stem(imgs: Tensor, wt: Tensor, shift: Tensor) -> Tensor:
+    """pm_resnet_stem: imgs f32 (N, 3, H, W), wt f32 (147, 64) (BatchNorm scale folded), shift f32 (64) ->
+    maxpool3x3/2(relu(conv7x7/2(imgs) + shift)) as bf16 NHWC (N, Hp, Wp, 64)."""
+    _cuda(imgs, wt, shift)
+    _need(imgs.dim() == 4 and imgs.shape[1] == 3 and imgs.dtype == torch.float32 and imgs.is_contiguous(),
+          "resnet_stem: imgs must be contiguous f32 (N, 3, H, W)")
+    _need(wt.shape == (147, 64) and wt.dtype == torch.float32 and wt.is_contiguous(), "resnet_stem: wt must be f32 (147, 64)")
+    _f32vec(shift, 64, "resnet_stem: shift")
+    N, _, H, W = imgs.shape
+    _need(H >= 1 and W >= 1, "resnet_stem: empty image")
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+    conv_map = torch.empty((N, Hc, Wc, 64), dtype=torch.bfloat16, device=imgs.device)
+    out = torch.empty((N, Hp, Wp, 64), dtype=torch.bfloat16, device=imgs.device)
+    rc = _launch("resnet_stem", (2.0 * 147 * 64 * N * Hc * Wc, float(imgs.numel() * 4 + 4 * conv_map.numel() + 2 * out.numel())),
+                 lambda: lib().pm_resnet_stem(imgs.data_ptr(), wt.data_ptr(), shift.data_ptr(), conv_map.data_ptr(), out.data_ptr(),
+                                              N, H, W, _stream()))
+    check(rc, f"pm_resnet_stem(N={N}, H={H}, W={W})")
+    return out
+
+
+def attention_hd32(q: Tensor, k: Tensor, v: Tensor, n_heads: int) -> Tensor:
+    """pm_attention_hd32_bf16: q (B, Lq, H*32), k / v (B, Lk, H*32) bf16 views with unit last stride (column slices of packed
+    projections, stride-0 batch broadcasts) -> softmax(q k^T / sqrt(32)) v as (B, Lq, H*32) bf16, heads merged.  No bias, not
+    causal.  (ops.attention's dispatch is unchanged: it sends head dim 32 to the generic kernel.)"""
+    _cuda(q, k, v)
+    _need(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention_hd32: operands must be (B, L, H*32)")
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    _need(D == n_heads * 32, f"attention_hd32: head dim must be 32 (got {D} / {n_heads})")
+    _need(k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention_hd32: shape mismatch")
+    _need(Lq >= 1 and Lk >= 1, "attention_hd32: empty sequence")
+    for t in (q, k, v):
+        _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention_hd32: bf16 operands with unit last stride")
+    out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
+    rc = _launch("attention_hd32", 4.0 * B * n_heads * Lq * Lk * 32, lambda: lib().pm_attention_hd32_bf16(
+        q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
+        out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, _stream()))
+    check(rc, f"pm_attention_hd32_bf16(B={B}, H={n_heads}, Lq={Lq}, Lk={Lk})")
     return out

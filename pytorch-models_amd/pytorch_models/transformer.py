@@ -359,7 +359,10 @@ class MLP(nn.Module):
 def _fused_attend(mha: MHA, x: Tensor, kv: Tensor | None, causal: bool, residual: Tensor) -> Tensor:
     if type(mha).forward is MHA.forward:  # plain MHA: residual add rides in the out_proj epilogue
         return mha.attend(x, kv, None, None, causal, residual=residual)
-    return residual + (mha(x, kv, causal=causal) if kv is not None else mha(x, causal=causal))  # subclassed MHA
+    # subclassed MHA: the reference calls sa(x) / sa(x, causal=True) / ca(x, memory) (transformer.py:98-100, 124) - `causal` is
+    # passed only where it is set, so a subclass whose forward has no such keyword (RelativeMHA.forward(self, x)) still fits
+    args = (x,) if kv is None else (x, kv)
+    return residual + (mha(*args, causal=True) if causal else mha(*args))
 
 
 def _fused_mlp(mlp: MLP, x: Tensor, residual: Tensor) -> Tensor:
