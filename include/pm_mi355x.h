@@ -476,6 +476,38 @@ int pm_attention_hd32_bf16(const void* q, int64_t q_stride_b, int64_t q_stride_t
                            int64_t k_stride_t, const void* v, int64_t v_stride_b, int64_t v_stride_t, void* o,
                            int64_t o_stride_b, int64_t o_stride_t, int64_t B, int64_t H, int64_t Lq, int64_t Lk, void* stream);
 
+/* ---- MLP-Mixer (reference: pytorch_models/image/mlp_mixer.py; csrc/mixer.hip).
+ * pm_mixer_token_mix_bf16: y = x + (W2 GELU(W1 LN(x)^T + b1) + b2)^T per image (mlp_mixer.py:30), one kernel on the bf16 MFMA.
+ * x, y: bf16 (N, T, C) contiguous; y may alias x.  stats: f32 (N*T, 2) [mean, rstd] of the rows of x (pm_ln_stats_finalize or
+ * pm_row_stats); gamma, beta: f32 (C), norm1; b1: f32 (Dt); b2: f32 (T).
+ * w1, w2: the weights W1 (Dt, T) and W2 (T, Dt) FRAGMENT-MAJOR, bf16: a matrix W (R, K) is zero-padded to R32 = R rounded up to
+ * 32 rows and K16 = K rounded up to 16 columns and stored as [R32/32 strips][K16/16 steps][64 lanes][8], lane l of strip s and
+ * step k holding W[32 s + (l & 31)][16 k + 8 (l >> 5) + 0..7] - the A operand of mfma_f32_32x32x16_bf16, so a wave's load is
+ * 1 KiB contiguous.  The zero padding is part of the contract (it is the K padding of the first product).
+ * LN(x) and the hidden activations are rounded to bf16, both products accumulate in fp32, the output is rounded once.
+ * row_out: NULL or f32 (N*T, C/64, 2): per row and 64-channel block (sum, sum of squares) of the bf16-rounded y, the layout
+ * pm_ln_stats_finalize reads.  Every image is computed alone (bit-identical at any batch size and position).
+ * C % 64 == 0, Dt % 32 == 0, and one image x 64 channels of LN(x) and of the hidden activations must fit the 160 KiB LDS:
+ * pm_mixer_token_mix_supported(T, Dt, C) (1 = served); N <= 65535.  All pointers 16-byte aligned (stats, row_out: 8). */
+int pm_mixer_token_mix_bf16(const void* x, const float* stats, const float* gamma, const float* beta, const void* w1,
+                            const float* b1, const void* w2, const float* b2, void* y, float* row_out, int64_t N, int64_t T,
+                            int64_t Dt, int64_t C, void* stream);
+int pm_mixer_token_mix_supported(int64_t T, int64_t Dt, int64_t C);
+
+/* pm_row_stats: stats[m] = (mean, rsqrt(biased variance + eps)) of row m of x (M, C), x_dtype rows with stride ldx: the format
+ * pm_ln_stats_finalize writes, for rows that no GEMM epilogue has summed.  fp32, centred second pass. */
+int pm_row_stats(const void* x, int64_t ldx, int x_dtype, float* stats, int64_t M, int64_t C, float eps, void* stream);
+
+/* pm_ln_mean: y[n, :] = mean over t < T of LayerNorm_C(x[n, t, :]) (mlp_mixer.py:58-59: norm, then the mean over tokens - not
+ * pm_mean_ln's mean-then-norm).  x (N, T, C) contiguous; stats (N*T, 2) as pm_row_stats writes them; y (N, C) contiguous. */
+int pm_ln_mean(const void* x, int x_dtype, const float* stats, const float* gamma, const float* beta, void* y, int y_dtype,
+               int64_t N, int64_t T, int64_t C, void* stream);
+
+/* pm_transpose_add_f32: y (N, Cc, R) = x (N, R, Cc) transposed per n [+ resid (N, Cc, R) when not NULL]; f32; x contiguous, the
+ * rows of y and resid ldy >= R apart (columns R .. ldy-1 are not written: a K padding that pm_linear_f32 never reads).
+ * The two transposes of the composed fp32 token mixing. */
+int pm_transpose_add_f32(const float* x, const float* resid, float* y, int64_t ldy, int64_t N, int64_t R, int64_t Cc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

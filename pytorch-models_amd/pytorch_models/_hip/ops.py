@@ -973,3 +973,99 @@ def attention_hd32(q: Tensor, k: Tensor, v: Tensor, n_heads: int) -> Tensor:
         out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, _stream()))
     check(rc, f"pm_attention_hd32_bf16(B={B}, H={n_heads}, Lq={Lq}, Lk={Lk})")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MLP-Mixer (csrc/mixer.hip)
+def mixer_token_mix_supported(T: int, Dt: int, C: int) -> bool:
+    return bool(lib().pm_mixer_token_mix_supported(T, Dt, C))
+
+
+def mixer_pack_weight(w: Tensor) -> Tensor:
+    """An nn.Linear weight (R, K) -> bf16 [ceil(R/32)][ceil(K/16)][64][8], the fragment-major, zero-padded form
+    pm_mixer_token_mix_bf16 reads (include/pm_mi355x.h): lane l of strip s, step k holds w[32 s + (l & 31)][16 k + 8 (l >> 5) + 0..7]."""
+    R, K = w.shape
+    R32, K16 = -(-R // 32) * 32, -(-K // 16) * 16
+    wp = torch.zeros((R32, K16), dtype=torch.bfloat16, device=w.device)
+    wp[:R, :K] = w.detach()
+    return wp.view(R32 // 32, 32, K16 // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().view(R32 // 32, K16 // 16, 64, 8)
+
+
+def mixer_token_mix(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, w1f: Tensor, b1: Tensor, w2f: Tensor, b2: Tensor, *,
+                    out: Tensor | None = None, want_row_stats: bool = False):
+    """pm_mixer_token_mix_bf16: x bf16 (N, T, C) -> x + token_mixing(LN(x)^T)^T, bf16 (``out`` may be x itself).  stats f32 (N*T, 2)
+    [mean, rstd] of x's rows; gamma / beta f32 (C); w1f = mixer_pack_weight(W1 (Dt, T)), w2f = mixer_pack_weight(W2 (T, Dt));
+    b1 f32 (Dt); b2 f32 (T).  want_row_stats=True also returns the (N*T, C/64, 2) partial statistics of the output rows
+    (ln_stats_finalize reads them)."""
+    _cuda(x, stats, gamma, beta, w1f, b1, w2f, b2, out)
+    _need(x.dim() == 3 and x.dtype == torch.bfloat16 and x.is_contiguous(), "mixer_token_mix: x must be contiguous bf16 (N, T, C)")
+    N, T, C = x.shape
+    Dt = b1.numel()
+    _need(C % 64 == 0 and C >= 64, f"mixer_token_mix: d_model must be a multiple of 64, got {C}")
+    _need(Dt % 32 == 0 and Dt >= 32, f"mixer_token_mix: the token-mixing hidden width must be a multiple of 32, got {Dt}")
+    _need(mixer_token_mix_supported(T, Dt, C),
+          f"mixer_token_mix: T={T} tokens with hidden width {Dt} do not fit: 64 channels of LN(x) and of the hidden activations, "
+          f"64 * 2 * ((T rounded up to 16) + 8 + Dt + 8) bytes, must fit the 160 KiB LDS")
+    _need(N <= 65535, "mixer_token_mix: at most 65535 images per call")
+    for w, shape, what in ((w1f, (Dt // 32, -(-T // 16), 64, 8), "w1f"), (w2f, (-(-T // 32), Dt // 16, 64, 8), "w2f")):
+        _need(w.dtype == torch.bfloat16 and tuple(w.shape) == shape and w.is_contiguous(),
+              f"mixer_token_mix: {what} must be mixer_pack_weight's bf16 {shape}, got {tuple(w.shape)}")
+    _need(stats.shape == (N * T, 2) and stats.dtype == torch.float32 and stats.is_contiguous(), "mixer_token_mix: stats must be f32 (N*T, 2)")
+    _f32vec(gamma, C, "mixer_token_mix: gamma")
+    _f32vec(beta, C, "mixer_token_mix: beta")
+    _f32vec(b1, Dt, "mixer_token_mix: b1")
+    _f32vec(b2, T, "mixer_token_mix: b2")
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out.shape == x.shape and out.dtype == torch.bfloat16 and out.is_contiguous(), "mixer_token_mix: out must be like x")
+    rows = torch.empty((N * T, C // 64, 2), dtype=torch.float32, device=x.device) if want_row_stats else None
+    work = (4.0 * N * C * w1f.shape[1] * 16 * Dt, float(4 * x.numel() + 2 * (w1f.numel() + w2f.numel())))
+    rc = _launch("mixer_token_mix", work, lambda: lib().pm_mixer_token_mix_bf16(
+        x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w1f.data_ptr(), b1.data_ptr(), w2f.data_ptr(),
+        b2.data_ptr(), out.data_ptr(), rows.data_ptr() if rows is not None else None, N, T, Dt, C, _stream()))
+    check(rc, f"pm_mixer_token_mix_bf16(N={N}, T={T}, Dt={Dt}, C={C})")
+    return (out, rows) if want_row_stats else out
+
+
+def row_stats(x: Tensor, eps: float) -> Tensor:
+    """pm_row_stats: x (M, C) bf16 | f32 rows (unit column stride) -> f32 (M, 2) [mean, rsqrt(var + eps)]."""
+    _cuda(x)
+    _need(x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= 1, "row_stats: x must be (M, C) rows")
+    M, C = x.shape
+    stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    rc = _launch("row_stats", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_row_stats(
+        x.data_ptr(), x.stride(0) if M > 1 else C, _dt(x), stats.data_ptr(), M, C, float(eps), _stream()))
+    check(rc, f"pm_row_stats(M={M}, C={C})")
+    return stats
+
+
+def ln_mean(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, out_dtype: torch.dtype) -> Tensor:
+    """pm_ln_mean: x (N, T, C) contiguous, stats (N*T, 2) of its rows -> (N, C) = mean over the tokens of LayerNorm_C(x)."""
+    _cuda(x, stats, gamma, beta)
+    _need(x.dim() == 3 and x.is_contiguous() and x.shape[1] >= 1, "ln_mean: x must be contiguous (N, T, C)")
+    N, T, C = x.shape
+    _need(stats.shape == (N * T, 2) and stats.dtype == torch.float32 and stats.is_contiguous(), "ln_mean: stats must be f32 (N*T, 2)")
+    _f32vec(gamma, C, "ln_mean: gamma")
+    _f32vec(beta, C, "ln_mean: beta")
+    _need(N <= 65535, "ln_mean: at most 65535 images per call")
+    out = torch.empty((N, C), dtype=out_dtype, device=x.device)
+    rc = _launch("ln_mean", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_ln_mean(
+        x.data_ptr(), _dt(x), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), _dt(out), N, T, C, _stream()))
+    check(rc, f"pm_ln_mean(N={N}, T={T}, C={C})")
+    return out
+
+
+def transpose_add_f32(x: Tensor, resid: Tensor | None = None, ldy: int | None = None) -> Tensor:
+    """pm_transpose_add_f32: x f32 (N, R, Cc) contiguous -> x transposed per n (+ resid of that shape), as the first R columns of
+    an (N, Cc, ldy) buffer (ldy defaults to R; the columns past R are left unwritten)."""
+    _cuda(x, resid)
+    _need(x.dim() == 3 and x.dtype == torch.float32 and x.is_contiguous(), "transpose_add_f32: x must be contiguous f32 (N, R, Cc)")
+    N, R, Cc = x.shape
+    ldy = R if ldy is None else ldy
+    _need(R >= 1 and Cc >= 1 and N <= 65535 and ldy >= R, "transpose_add_f32: empty rows, more than 65535 images or ldy < R")
+    _need(resid is None or (resid.shape == (N, Cc, R) and resid.dtype == torch.float32 and resid.stride() == (Cc * ldy, ldy, 1)),
+          "transpose_add_f32: resid must be f32 (N, Cc, R) with the output's strides")
+    out = torch.empty((N, Cc, ldy), dtype=torch.float32, device=x.device)[:, :, :R]
+    rc = _launch("transpose_add_f32", (0.0, float(x.numel() * 4 * (3 if resid is not None else 2))), lambda: lib().pm_transpose_add_f32(
+        x.data_ptr(), resid.data_ptr() if resid is not None else None, out.data_ptr(), ldy, N, R, Cc, _stream()))
+    check(rc, f"pm_transpose_add_f32(N={N}, R={R}, Cc={Cc})")
+    return out

@@ -48,6 +48,13 @@ def _flax_norm(ln: nn.LayerNorm, w: dict, key: str) -> None:
     ln.bias.copy_(w.pop(key + "/bias"))
 
 
+def _flax_conv2d(conv: nn.Conv2d, w: dict, key: str) -> None:
+    """Flax Conv: kernel is (kh, kw, in, out) -> nn.Conv2d (out, in, kh, kw)."""
+    conv.weight.copy_(w.pop(key + "/kernel").permute(3, 2, 0, 1))
+    if conv.bias is not None:
+        conv.bias.copy_(w.pop(key + "/bias"))
+
+
 def _flax_attention(mha, w: dict, key: str) -> None:
     for ours, theirs in (("q_proj", "query"), ("k_proj", "key"), ("v_proj", "value"), ("out_proj", "out")):
         _flax_dense(getattr(mha, ours), w, f"{key}/{theirs}")

@@ -187,6 +187,27 @@ class ViT(nn.Module):
         return m
 
 
+def load_flax_ln(norm: nn.LayerNorm, weights: dict[str, Tensor], prefix: str) -> None:
+    """Flax LayerNorm ``{prefix}/scale``, ``{prefix}/bias`` -> ``norm`` (the keys are popped, as in the reference)."""
+    from ..converters import _flax_norm
+
+    _flax_norm(norm, weights, prefix)
+
+
+def load_flax_linear(linear: nn.Linear, weights: dict[str, Tensor], prefix: str) -> None:
+    """Flax Dense ``{prefix}/kernel`` (in, out) [+ ``{prefix}/bias``] -> ``linear`` (out, in)."""
+    from ..converters import _flax_dense
+
+    _flax_dense(linear, weights, prefix)
+
+
+def load_flax_conv2d(conv2d: nn.Conv2d, weights: dict[str, Tensor], prefix: str) -> None:
+    """Flax Conv ``{prefix}/kernel`` (kh, kw, in, out) [+ ``{prefix}/bias``] -> ``conv2d`` (out, in, kh, kw)."""
+    from ..converters import _flax_conv2d
+
+    _flax_conv2d(conv2d, weights, prefix)
+
+
 def _no_download(who: str):
     raise NotImplementedError(
         f"{who}(pretrained=True) needs a network download, which this build does not do; construct with "
