@@ -508,6 +508,58 @@ int pm_ln_mean(const void* x, int x_dtype, const float* stats, const float* gamm
  * The two transposes of the composed fp32 token mixing. */
 int pm_transpose_add_f32(const float* x, const float* resid, float* y, int64_t ldy, int64_t N, int64_t R, int64_t Cc, void* stream);
 
+/* ---- EnCodec (reference: pytorch_models/audio/encodec.py; csrc/encodec.hip).  Everything fp32 on the exact-product f32 MFMA;
+ * activations TIME-MAJOR (B, T, C).
+ * pm_conv1d_f32: a 1-D convolution as an implicit GEMM.  x: clip b at x + b * x_batch_stride, (Tin, Cin) contiguous.
+ * w: (up * Cout, k * Cin) row-major, column tap * Cin + ci.  Row m < Mr = (Tin + left + right - k) / stride + 1 of the product
+ * reads the frames m * stride - left .. + k - 1: beyond the clip they are MIRRORED (F.pad "reflect"; left, right < Tin; right
+ * includes the extra padding that rounds the length up to the stride) or, zero_pad != 0, zero.  elu != 0: ELU on the operand as
+ * it is loaded.  Column n of the product is channel n % Cout of output frame m * up + n / Cout - trim; frames outside
+ * [0, Tout) are dropped.  y, resid: (B, Tout, Cout) contiguous; bias (Cout) and resid (up == 1, trim == 0 only) may be NULL.
+ * Conv1d: up = 1, trim = 0, Tout = Mr.  ConvTranspose1d(kernel 2 s, stride s) + Unpad1d: k = 2, stride = 1, left = right = 1,
+ * zero_pad = 1, up = s, w[r * Cout + co][j * Cin + ci] = weight[ci][co][r + (1 - j) * s], trim = the left trim.
+ * Cin % 4 == 0 takes 16-byte loads (x, w 16-byte aligned, x_batch_stride % 4 == 0), Cout % 4 == 0 16-byte stores.
+ * pm_conv1d_f32_supported: 1 when the geometry is served. */
+int pm_conv1d_f32(const float* x, int64_t x_batch_stride, const float* w, const float* bias, const float* resid, float* y,
+                  int64_t B, int64_t Tin, int64_t Cin, int64_t Cout, int64_t k, int64_t stride, int64_t left, int64_t right,
+                  int zero_pad, int elu, int64_t up, int64_t trim, int64_t Tout, void* stream);
+int pm_conv1d_f32_supported(int64_t Tin, int64_t Cin, int64_t Cout, int64_t k, int64_t stride, int64_t left, int64_t right,
+                            int zero_pad, int64_t up);
+
+/* pm_lstm_f32: n_layers stacked LSTM layers (nn.LSTM: gates i, f, g, o; zero initial state) over x (B, T, H) time-major, input
+ * size == hidden size H (H % 64 == 0).  w_ih, w_hh, bias: HOST arrays of n_layers device pointers: (4H, H), (4H, H) and
+ * bias_ih + bias_hh (4H).  y (B, T, H) = the last layer's h (+ x when flags & 1).  ONE LAUNCH PER STEP, no grid-wide wait of any
+ * kind.  Two layers run as a wavefront: one pm_linear_f32 for layer 0's input projections of all frames, then T + 1 launches in
+ * which layer 0 at frame s runs beside layer 1 at frame s - 1 (layer 1 multiplies [h0, h1_prev] with [W_ih; W_hh] itself).
+ * flags & 2, or another number of layers: plain passes, per layer one pm_linear_f32 and T launches.  Every launch goes to `stream`,
+ * so the call can be captured in a graph.  work: pm_lstm_workspace_floats(B, T, H) floats, 16-byte aligned.  Rows of the batch are
+ * independent: row i is bit-identical at any batch size. */
+int pm_lstm_f32(const float* x, const float* const* w_ih, const float* const* w_hh, const float* const* bias, int64_t n_layers,
+                float* work, float* y, int flags, int64_t B, int64_t T, int64_t H, void* stream);
+int64_t pm_lstm_workspace_floats(int64_t B, int64_t T, int64_t H);
+
+/* pm_rvq_encode_f32: residual vector quantization of z (M, dim) with the first n_q of codebooks (n_q, codebook_size, dim);
+ * norms (n_q, codebook_size) = the squared norms of the entries.  Per stage: argmin of |e|^2 - 2 r.e (lowest index on exact
+ * ties), r -= e.  codes: int64 (n_q, M).  dim == 128 and codebook_size == 1024 only.
+ * pm_rvq_decode_f32: out (B * T, dim) = sum over q < n_q, in stage order, of codebooks[q][codes[b * stride_b + q * stride_q +
+ * t * stride_t]] (indices outside the codebook are clamped into it). */
+int pm_rvq_encode_f32(const float* z, const float* codebooks, const float* norms, int64_t* codes, int64_t M, int64_t n_q,
+                      int64_t dim, int64_t codebook_size, void* stream);
+int pm_rvq_decode_f32(const int64_t* codes, int64_t stride_b, int64_t stride_q, int64_t stride_t, const float* codebooks,
+                      float* out, int64_t B, int64_t T, int64_t n_q, int64_t dim, int64_t codebook_size, void* stream);
+
+/* pm_groupnorm1_f32: GroupNorm(1, C) of B clips in place: x (B, n) with n = T * C time-major (channel = index % C), biased
+ * variance over the whole clip, per-channel affine, + resid (B, n) when not NULL.  Partial sums of 64 floats per thread in fp32,
+ * combined in fp64.  work: pm_groupnorm1_workspace_doubles(B, n) doubles.  B <= 65535. */
+int pm_groupnorm1_f32(float* x, const float* gamma, const float* beta, const float* resid, double* work, int64_t B, int64_t n,
+                      int64_t C, float eps, void* stream);
+int64_t pm_groupnorm1_workspace_doubles(int64_t B, int64_t n);
+
+/* pm_encodec_scale_f32: scale[b] = sqrt(mean_t(mean_c(x[b, c, t])^2)) + 1e-8 of x (B, C, T) (encodec.py:198).
+ * pm_scale_clips_f32: y[b, i] = x[b, i] / scale[b] (divide != 0) or x[b, i] * scale[b], i < n; y may alias x.  B <= 65535. */
+int pm_encodec_scale_f32(const float* x, float* scale, int64_t B, int64_t C, int64_t T, void* stream);
+int pm_scale_clips_f32(const float* x, const float* scale, float* y, int64_t B, int64_t n, int divide, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,16 @@ SIGNATURES = {
     "pm_row_stats": ([_p, _l, _i, _p, _l, _l, _f, _p], c_int),
     "pm_ln_mean": ([_p, _i, _p, _p, _p, _p, _i, _l, _l, _l, _p], c_int),
     "pm_transpose_add_f32": ([_p, _p, _p, _l, _l, _l, _l, _p], c_int),
+    "pm_conv1d_f32": ([_p, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _l, _l, _l, _p], c_int),
+    "pm_conv1d_f32_supported": ([_l, _l, _l, _l, _l, _l, _l, _i, _l], c_int),
+    "pm_lstm_f32": ([_p, _p, _p, _p, _l, _p, _p, _i, _l, _l, _l, _p], c_int),
+    "pm_lstm_workspace_floats": ([_l, _l, _l], c_int64),
+    "pm_rvq_encode_f32": ([_p, _p, _p, _p, _l, _l, _l, _l, _p], c_int),
+    "pm_rvq_decode_f32": ([_p, _l, _l, _l, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_groupnorm1_f32": ([_p, _p, _p, _p, _p, _l, _l, _l, _f, _p], c_int),
+    "pm_groupnorm1_workspace_doubles": ([_l, _l], c_int64),
+    "pm_encodec_scale_f32": ([_p, _p, _l, _l, _l, _p], c_int),
+    "pm_scale_clips_f32": ([_p, _p, _p, _l, _l, _i, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

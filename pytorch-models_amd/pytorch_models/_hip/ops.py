@@ -1069,3 +1069,148 @@ def transpose_add_f32(x: Tensor, resid: Tensor | None = None, ldy: int | None = 
         x.data_ptr(), resid.data_ptr() if resid is not None else None, out.data_ptr(), ldy, N, R, Cc, _stream()))
     check(rc, f"pm_transpose_add_f32(N={N}, R={R}, Cc={Cc})")
     return out
+
+
+# ---- EnCodec (csrc/encodec.hip): fp32, activations time-major (B, T, C)
+def _f32c(t: Tensor, what: str) -> None:
+    _need(t.dtype == torch.float32 and t.is_contiguous(), f"{what} must be contiguous f32")
+
+
+def conv1d_supported(Tin: int, Cin: int, Cout: int, k: int, stride: int, left: int, right: int, zero_pad: bool = False, up: int = 1) -> bool:
+    return bool(lib().pm_conv1d_f32_supported(Tin, Cin, Cout, k, stride, left, right, int(zero_pad), up))
+
+
+def conv1d_f32(x: Tensor, w: Tensor, bias: Tensor | None, *, k: int, stride: int = 1, left: int = 0, right: int = 0, elu: bool = False,
+               resid: Tensor | None = None, zero_pad: bool = False, up: int = 1, trim: int = 0, t_out: int | None = None) -> Tensor:
+    """pm_conv1d_f32: x f32 (B, Tin, Cin) time-major (clips may be a time slice of a larger buffer: strides (any, Cin, 1)), w f32
+    (up * Cout, k * Cin) with column tap * Cin + ci -> (B, Tout, Cout).  ``left`` / ``right`` are mirrored (or zero) frames, ``right``
+    including the extra padding; ``elu`` applies ELU to the operand as it is loaded; ``resid`` (B, Tout, Cout) is added in the
+    epilogue.  ``up`` / ``trim`` / ``zero_pad``: the transposed-convolution form (include/pm_mi355x.h)."""
+    _cuda(x, w, bias, resid)
+    _need(x.dim() == 3 and x.dtype == torch.float32, "conv1d_f32: x must be f32 (B, Tin, Cin) time-major")
+    B, Tin, Cin = x.shape
+    _need((Cin == 1 or x.stride(2) == 1) and (Tin == 1 or x.stride(1) == Cin), "conv1d_f32: x must be f32 (B, Tin, Cin) time-major")  # (a dimension of one has no stride to speak of)
+    _f32c(w, "conv1d_f32: w")
+    _need(w.dim() == 2 and w.shape[1] == k * Cin and w.shape[0] % up == 0, f"conv1d_f32: w {tuple(w.shape)} is not (up * Cout, {k} * {Cin})")
+    Cout = w.shape[0] // up
+    _need(conv1d_supported(Tin, Cin, Cout, k, stride, left, right, zero_pad, up),
+          f"conv1d_f32: {Tin} frames with padding ({left}, {right}), kernel {k}, stride {stride} are not served (reflect padding must be shorter than the clip)")
+    Mr = (Tin + left + right - k) // stride + 1
+    Tout = Mr * up - trim if t_out is None else t_out
+    _need(1 <= Tout <= Mr * up, "conv1d_f32: bad output length")
+    if bias is not None:
+        _f32vec(bias, Cout, "conv1d_f32: bias")
+    if resid is not None:
+        _need(resid.shape == (B, Tout, Cout) and up == 1 and trim == 0, "conv1d_f32: resid must be (B, Tout, Cout)")
+        _f32c(resid, "conv1d_f32: resid")
+    out = torch.empty((B, Tout, Cout), dtype=torch.float32, device=x.device)
+    rc = _launch("conv1d_f32", 2.0 * B * Mr * w.shape[0] * w.shape[1], lambda: lib().pm_conv1d_f32(
+        x.data_ptr(), x.stride(0) if B > 1 else Tin * Cin, w.data_ptr(), bias.data_ptr() if bias is not None else None,
+        resid.data_ptr() if resid is not None else None, out.data_ptr(), B, Tin, Cin, Cout, k, stride, left, right, int(zero_pad),
+        int(elu), up, trim, Tout, _stream()))
+    check(rc, f"pm_conv1d_f32(B={B}, Tin={Tin}, Cin={Cin}, Cout={Cout}, k={k}, stride={stride}, up={up})")
+    return out
+
+
+def lstm_f32(x: Tensor, w_ih: list[Tensor], w_hh: list[Tensor], bias: list[Tensor], residual: bool = False, plain: bool = False) -> Tensor:
+    """pm_lstm_f32: x f32 (B, T, H) time-major through len(w_ih) stacked LSTM layers (nn.LSTM's gate order; ``bias`` = bias_ih +
+    bias_hh per layer) -> the last layer's h (+ x when ``residual``).  One ctypes call.  Two layers run as a wavefront (one GEMM,
+    T + 1 launches); ``plain`` forces a GEMM and T step launches per layer (kept for the comparison in tools/encodec_bench.py)."""
+    import ctypes
+
+    _cuda(x, *w_ih, *w_hh, *bias)
+    _need(x.dim() == 3, "lstm_f32: x must be (B, T, H)")
+    _f32c(x, "lstm_f32: x")
+    B, T, H = x.shape
+    n = len(w_ih)
+    _need(n >= 1 and len(w_hh) == n and len(bias) == n and T >= 1, "lstm_f32: one (w_ih, w_hh, bias) per layer, T >= 1")
+    _need(H % 64 == 0 and H >= 64, f"lstm_f32: the hidden size must be a multiple of 64 (got {H})")
+    for a, b_, c in zip(w_ih, w_hh, bias):
+        _need(a.shape == (4 * H, H) and b_.shape == (4 * H, H) and c.shape == (4 * H,), "lstm_f32: weights must be (4H, H), input size == hidden size")
+        for t in (a, b_, c):
+            _f32c(t, "lstm_f32: weights")
+    work = torch.empty((lib().pm_lstm_workspace_floats(B, T, H),), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
+    rc = _launch("lstm_f32", 2.0 * B * T * 8 * H * H * n, lambda: lib().pm_lstm_f32(
+        x.data_ptr(), arr(w_ih), arr(w_hh), arr(bias), n, work.data_ptr(), out.data_ptr(), int(residual) | (2 if plain else 0), B, T, H, _stream()))
+    check(rc, f"pm_lstm_f32(B={B}, T={T}, H={H}, layers={n})")
+    return out
+
+
+def rvq_encode(z: Tensor, codebooks: Tensor, norms: Tensor, n_q: int) -> Tensor:
+    """pm_rvq_encode_f32: z f32 (M, 128) rows, codebooks (Q, 1024, 128), norms (Q, 1024) -> int64 codes (n_q, M)."""
+    _cuda(z, codebooks, norms)
+    _need(z.dim() == 2 and codebooks.dim() == 3 and z.shape[1] == codebooks.shape[2], "rvq_encode: z (M, D), codebooks (Q, N, D)")
+    for t in (z, codebooks, norms):
+        _f32c(t, "rvq_encode: operands")
+    Q, N, D = codebooks.shape
+    _need(1 <= n_q <= Q and norms.shape == (Q, N), f"rvq_encode: n_quantizers must be in 1..{Q}")
+    M = z.shape[0]
+    codes = torch.empty((n_q, M), dtype=torch.int64, device=z.device)
+    rc = _launch("rvq_encode_f32", 2.0 * M * N * D * n_q, lambda: lib().pm_rvq_encode_f32(
+        z.data_ptr(), codebooks.data_ptr(), norms.data_ptr(), codes.data_ptr(), M, n_q, D, N, _stream()))
+    check(rc, f"pm_rvq_encode_f32(M={M}, n_q={n_q}, dim={D}, codebook={N})")
+    return codes
+
+
+def rvq_decode(codes: Tensor, codebooks: Tensor) -> Tensor:
+    """pm_rvq_decode_f32: int64 codes (B, n_q, T) (any strides), codebooks (Q, 1024, 128) -> f32 (B, T, 128) time-major."""
+    _cuda(codes, codebooks)
+    _need(codes.dim() == 3 and codes.dtype == torch.int64, "rvq_decode: codes must be int64 (B, n_q, T)")
+    _f32c(codebooks, "rvq_decode: codebooks")
+    B, n_q, T = codes.shape
+    Q, N, D = codebooks.shape
+    _need(1 <= n_q <= Q, f"rvq_decode: {n_q} code streams for {Q} codebooks")
+    out = torch.empty((B, T, D), dtype=torch.float32, device=codes.device)
+    rc = _launch("rvq_decode_f32", (0.0, float(out.numel() * 4 * (n_q + 1))), lambda: lib().pm_rvq_decode_f32(
+        codes.data_ptr(), codes.stride(0), codes.stride(1), codes.stride(2), codebooks.data_ptr(), out.data_ptr(), B, T, n_q, D, N, _stream()))
+    check(rc, f"pm_rvq_decode_f32(B={B}, T={T}, n_q={n_q})")
+    return out
+
+
+def groupnorm1_(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, resid: Tensor | None = None) -> Tensor:
+    """pm_groupnorm1_f32: GroupNorm(1, C) of x f32 (B, T, C) contiguous IN PLACE (statistics over the whole clip), + resid."""
+    _cuda(x, gamma, beta, resid)
+    _need(x.dim() == 3, "groupnorm1_: x must be (B, T, C)")
+    _f32c(x, "groupnorm1_: x")
+    B, T, C = x.shape
+    _f32vec(gamma, C, "groupnorm1_: gamma")
+    _f32vec(beta, C, "groupnorm1_: beta")
+    if resid is not None:
+        _need(resid.shape == x.shape, "groupnorm1_: resid must have x's shape")
+        _f32c(resid, "groupnorm1_: resid")
+    _need(B <= 65535 and T >= 1, "groupnorm1_: at most 65535 clips, at least one frame")
+    work = torch.empty((lib().pm_groupnorm1_workspace_doubles(B, T * C),), dtype=torch.float64, device=x.device)
+    rc = _launch("groupnorm1_f32", (0.0, float(x.numel() * 12)), lambda: lib().pm_groupnorm1_f32(
+        x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), resid.data_ptr() if resid is not None else None, work.data_ptr(), B, T * C, C,
+        float(eps), _stream()))
+    check(rc, f"pm_groupnorm1_f32(B={B}, T={T}, C={C})")
+    return x
+
+
+def encodec_scale(x: Tensor) -> Tensor:
+    """pm_encodec_scale_f32: x f32 (B, C, T) -> (B, 1, 1): sqrt(mean_t(mean_c(x)^2)) + 1e-8."""
+    _cuda(x)
+    _need(x.dim() == 3, "encodec_scale: x must be (B, C, T)")
+    _f32c(x, "encodec_scale: x")
+    B, C, T = x.shape
+    _need(T >= 1 and C >= 1, "encodec_scale: empty clip")
+    out = torch.empty((B, 1, 1), dtype=torch.float32, device=x.device)
+    rc = _launch("encodec_scale_f32", (0.0, float(x.numel() * 4)), lambda: lib().pm_encodec_scale_f32(x.data_ptr(), out.data_ptr(), B, C, T, _stream()))
+    check(rc, f"pm_encodec_scale_f32(B={B}, C={C}, T={T})")
+    return out
+
+
+def scale_clips(x: Tensor, scale: Tensor, divide: bool) -> Tensor:
+    """pm_scale_clips_f32: x f32 (B, ...) contiguous divided (or multiplied) by scale[b]."""
+    _cuda(x, scale)
+    _f32c(x, "scale_clips: x")
+    _f32c(scale, "scale_clips: scale")
+    B = x.shape[0]
+    _need(x.dim() >= 2 and scale.numel() == B and B <= 65535 and x.numel() > 0, "scale_clips: one scale per clip, at most 65535 clips")
+    out = torch.empty_like(x)
+    rc = _launch("scale_clips_f32", (0.0, float(x.numel() * 8)), lambda: lib().pm_scale_clips_f32(
+        x.data_ptr(), scale.data_ptr(), out.data_ptr(), B, x.numel() // B, int(divide), _stream()))
+    check(rc, "pm_scale_clips_f32")
+    return out

@@ -1,7 +1,8 @@
-"""Audio encoders: Wav2Vec2 / HuBERT, data2vec-audio, SEW.  Same import path and class names as
-/root/reference pytorch_models/audio/__init__.py (EnCodec is not built)."""
+"""Audio models: Wav2Vec2 / HuBERT, data2vec-audio, SEW and the EnCodec codec.  Same import paths and class
+names as the reference's pytorch_models/audio/__init__.py."""
 from .data2vec_audio import Data2VecAudio
+from .encodec import EnCodec, EnCodecDecoder, EnCodecEncoder
 from .sew import SEW
 from .wav2vec2 import Wav2Vec2
 
-__all__ = ["Data2VecAudio", "SEW", "Wav2Vec2"]
+__all__ = ["Data2VecAudio", "EnCodec", "EnCodecDecoder", "EnCodecEncoder", "SEW", "Wav2Vec2"]
