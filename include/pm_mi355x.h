@@ -560,6 +560,43 @@ int64_t pm_groupnorm1_workspace_doubles(int64_t B, int64_t n);
 int pm_encodec_scale_f32(const float* x, float* scale, int64_t B, int64_t C, int64_t T, void* stream);
 int pm_scale_clips_f32(const float* x, const float* scale, float* y, int64_t B, int64_t n, int divide, void* stream);
 
+/* ---- KV-cached T5 decode step (text/t5.py: T5Model.generate), csrc/decode_t5.hip.  The stages whose form differs from the
+ * pm_dec_* step: RMS norm without centring or bias (gamma f32 (d), eps), bias-free projections (bf16 weights, K-contiguous rows
+ * of d), inner = H * 64 independent of d, a relative-position bias on the self-attention scores, a gated MLP, eos bookkeeping.
+ * x: f32 (B, d) contiguous, B <= 64, d % 8 == 0, d <= 1024; all pointers 16-byte aligned.  Every result of sequence b depends
+ * on sequence b alone, in one fixed summation order.
+ *
+ * pm_t5_dec_self_fused: one workgroup per (b, h): [q|k|v] = rmsnorm(x[b]) w_qkv[{q,k,v} rows of head h]^T (w_qkv (3 * inner, d)),
+ *   k / v rounded to bf16 into kcache / vcache (B, H, Tmax, 64) at t = *pos_ptr, then softmax_j(q k_j / 8 + lut[h, t - j]) v_j over
+ *   j <= t -> att f32 (B, inner).  lut: f32 (H, Tmax), the one-sided relative-position bias by distance.  Tmax <= 2048.
+ * pm_t5_dec_rms_qkv + pm_t5_dec_self_attention: the same result as two launches (the projection reads w_qkv once per 8 sequences;
+ *   q: f32 (B, inner) scratch) - for B * H beyond the number of compute units.
+ * pm_t5_dec_cross_fused: q = rmsnorm(x[b]) w_q[rows of head h]^T over the first src_len[b] (int32 (B), clamped to S) keys of
+ *   cross_kv bf16 (B, S, [k | v]) (2 * inner per key); src_len[b] == 0 -> zeros.  S <= 2048.
+ * pm_t5_dec_geglu: h[b, f] = gelu_tanh(rmsnorm(x[b]) . w_wv[2 f]) * (rmsnorm(x[b]) . w_wv[2 f + 1]): w_wv (2 F, d) holds the
+ *   gate row and the value row of feature f next to each other; h f32, row stride ldh.  F % 8 == 0.
+ * pm_t5_dec_next_token: per sequence the winner of the (n_tiles) tile winners pm_dec_linear mode 2 left (lowest index on ties);
+ *   position t + 1 (t = *pos_ptr) gets prompt[b, t + 1] while t + 1 < P, pad_id once finished[b], else the winner, and a winner
+ *   equal to eos_id >= 0 sets finished[b] (int32) and out_lengths[b] = t + 2 (int64); tokens (B, Ttot) int64; x[b] = emb[token]
+ *   (no positional term); logits_all != NULL: logits_step (B, V) f32 is copied to logits_all[b, t, :] of (B, Ttot - 1, V); the last
+ *   workgroup (agent-scope ticket, *ticket zero before and after) stores t + 1 to *pos_ptr.
+ * pm_t5_dec_embed: x[b] = emb[tok[b * ldtok]] (before a run's first step). */
+int pm_t5_dec_embed(const int64_t* tok, int64_t ldtok, const void* emb, float* x, int64_t B, int64_t d, int64_t V, void* stream);
+int pm_t5_dec_self_fused(const float* x, int64_t d, const float* gamma, float eps, const void* w_qkv, void* kcache, void* vcache,
+                         int64_t Tmax, const int32_t* pos_ptr, const float* lut, float* att, int64_t B, int64_t H, void* stream);
+int pm_t5_dec_rms_qkv(const float* x, int64_t d, const float* gamma, float eps, const void* w_qkv, float* q, void* kcache,
+                      void* vcache, int64_t Tmax, const int32_t* pos_ptr, int64_t B, int64_t H, void* stream);
+int pm_t5_dec_self_attention(const float* q, const void* kcache, const void* vcache, int64_t Tmax, const int32_t* pos_ptr,
+                             const float* lut, float* att, int64_t B, int64_t H, void* stream);
+int pm_t5_dec_cross_fused(const float* x, int64_t d, const float* gamma, float eps, const void* w_q, const void* cross_kv,
+                          int64_t S, const int32_t* src_len, float* att, int64_t B, int64_t H, void* stream);
+int pm_t5_dec_geglu(const float* x, int64_t d, const float* gamma, float eps, const void* w_wv, float* h, int64_t ldh, int64_t B,
+                    int64_t F, void* stream);
+int pm_t5_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr, const int64_t* prompt,
+                         int64_t P, int64_t* tokens, int64_t Ttot, int64_t pad_id, int64_t eos_id, int32_t* finished,
+                         int64_t* out_lengths, const void* emb, float* x, int64_t d, int64_t V, int32_t* ticket,
+                         const float* logits_step, float* logits_all, int64_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,13 @@ SIGNATURES = {
     "pm_groupnorm1_workspace_doubles": ([_l, _l], c_int64),
     "pm_encodec_scale_f32": ([_p, _p, _l, _l, _l, _p], c_int),
     "pm_scale_clips_f32": ([_p, _p, _p, _l, _l, _i, _p], c_int),
+    "pm_t5_dec_embed": ([_p, _l, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_t5_dec_self_fused": ([_p, _l, _p, _f, _p, _p, _p, _l, _p, _p, _p, _l, _l, _p], c_int),
+    "pm_t5_dec_rms_qkv": ([_p, _l, _p, _f, _p, _p, _p, _p, _l, _p, _l, _l, _p], c_int),
+    "pm_t5_dec_self_attention": ([_p, _p, _p, _l, _p, _p, _p, _l, _l, _p], c_int),
+    "pm_t5_dec_cross_fused": ([_p, _l, _p, _f, _p, _p, _l, _p, _p, _l, _l, _p], c_int),
+    "pm_t5_dec_geglu": ([_p, _l, _p, _f, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_t5_dec_next_token": ([_p, _p, _l, _p, _p, _l, _p, _l, _l, _l, _p, _p, _p, _p, _l, _l, _p, _p, _p, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

@@ -188,6 +188,21 @@ class T5Model(nn.Module):
                 break
         return torch.tensor(out, device=input_ids.device)
 
+    @torch.no_grad()
+    def generate(self, input_ids: Tensor, *, lengths=None, max_new_tokens: int = 100, pad_id: int = 0, eos_id: int = 1,
+                 decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False):
+        """Batched greedy generation with a KV cache (text/t5_generate.py over csrc/decode_t5.hip): the loop of generate_ids per
+        row of a right-padded batch.  input_ids int64 (B, S); lengths (B,) tensor or list, None = every row is full;
+        decoder_prompt int64 (B, P), teacher-forced, default one column of pad_id.  Returns ids (B, P + max_new_tokens) int64 and
+        out_lengths (B,) int64 - a row that has produced eos_id emits pad_id from then on and its length counts up to and
+        including the eos (eos_id < 0 never stops) - and with return_logits the fp32 last-position logits of every step,
+        (B, P + max_new_tokens - 1, vocab).  graph=True captures one step into a HIP graph and replays it; graph=False issues
+        the same launches eagerly.  bf16 parameters, at most 64 sequences, d_model <= 1024 (small / base / large)."""
+        from .t5_generate import generate
+
+        return generate(self, input_ids, lengths=lengths, max_new_tokens=max_new_tokens, pad_id=pad_id, eos_id=eos_id,
+                        decoder_prompt=decoder_prompt, graph=graph, return_logits=return_logits)
+
     @staticmethod
     def from_t5x(model_tag: str, *, pretrained: bool = False, **kwargs) -> "T5Model":
         variant, size = model_tag.split("-")
