@@ -597,6 +597,25 @@ int pm_t5_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_t
                          int64_t* out_lengths, const void* emb, float* x, int64_t d, int64_t V, int32_t* ticket,
                          const float* logits_step, float* logits_all, int64_t B, void* stream);
 
+/* ---- Class-token tail (csrc/cls_tail.hip): the last encoder layer of a class-token ViT for ONE query per image and head,
+ * without projecting K or V.  With W'k, W'v the k / v weights with the layer's sa_norm gamma folded in and (mean_j, rstd_j)
+ * the sa_norm statistics of the stored rows x_j: u_h = W'k,h^T q_h, p_hj = softmax_j(scale rstd_j (u_h . x_j - mean_j sum(u_h))),
+ * ctx_h = sum_j p_hj rstd_j (x_j - mean_j), o_h = W'v,h ctx_h + (W_v beta + b_v)_h.
+ * pm_cls_attend: x bf16, N images of L rows of d (row stride x_row_stride, image stride x_batch_stride, elements; both % 8);
+ *   stats f32 (N*L, 2) [mean, rstd] of the rows (pm_ln_stats_finalize / pm_row_stats), or NULL: the kernel computes them with
+ *   eps in the pass it makes anyway; u bf16 (N, H, d) contiguous; ctx bf16 (N, H, d) contiguous.  One workgroup per image: the
+ *   result of an image does not depend on N or on its position.  d % 64 == 0, H <= 16 (else PM_EINVAL); d <= 1024 (else
+ *   PM_EUNSUPPORTED; pm_cls_attend_supported(L, d, H) = 1 where served).  x, u 16-byte aligned; ctx, stats 8.
+ * pm_cls_head_gemm: y[m, g, :] = x[m, g, :] w[g]^T (+ bias[g]) for g < G in one launch: x bf16, row m of group g = K elements at
+ *   x + m ldx + g x_group_stride; w bf16 (G, N, K) contiguous; bias f32 (G, N) or NULL; y bf16 at y + m ldy + g y_group_stride.
+ *   N % 64 == 0, K % 32 == 0.  fp32 accumulation in a fixed order per element: a row's result does not depend on M or on the
+ *   row's position. */
+int pm_cls_attend(const void* x, int64_t x_row_stride, int64_t x_batch_stride, const float* stats, const void* u, void* ctx,
+                  int64_t N, int64_t L, int64_t d, int64_t H, float scale, float eps, void* stream);
+int pm_cls_attend_supported(int64_t L, int64_t d, int64_t H);
+int pm_cls_head_gemm(const void* x, int64_t ldx, int64_t x_group_stride, const void* w, const float* bias, void* y, int64_t ldy,
+                     int64_t y_group_stride, int64_t M, int64_t N, int64_t K, int64_t G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

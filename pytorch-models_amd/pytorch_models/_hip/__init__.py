@@ -104,6 +104,9 @@ SIGNATURES = {
     "pm_t5_dec_cross_fused": ([_p, _l, _p, _f, _p, _p, _l, _p, _p, _l, _l, _p], c_int),
     "pm_t5_dec_geglu": ([_p, _l, _p, _f, _p, _p, _l, _l, _l, _p], c_int),
     "pm_t5_dec_next_token": ([_p, _p, _l, _p, _p, _l, _p, _l, _l, _l, _p, _p, _p, _p, _l, _l, _p, _p, _p, _l, _p], c_int),
+    "pm_cls_attend": ([_p, _l, _l, _p, _p, _p, _l, _l, _l, _l, _f, _f, _p], c_int),
+    "pm_cls_attend_supported": ([_l, _l, _l], c_int),
+    "pm_cls_head_gemm": ([_p, _l, _l, _p, _p, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

@@ -1214,3 +1214,45 @@ def scale_clips(x: Tensor, scale: Tensor, divide: bool) -> Tensor:
         x.data_ptr(), scale.data_ptr(), out.data_ptr(), B, x.numel() // B, int(divide), _stream()))
     check(rc, "pm_scale_clips_f32")
     return out
+
+
+def cls_attend_supported(L: int, d: int, H: int) -> bool:
+    return bool(lib().pm_cls_attend_supported(L, d, H))
+
+
+def cls_head_gemm(x: Tensor, w: Tensor, bias: Tensor | None = None) -> Tensor:
+    """pm_cls_head_gemm: x bf16 (M, G, K) or (M, G*K) rows, w bf16 (G, N, K), bias f32 (G*N) | None -> bf16 (M, G, N):
+    y[:, g] = x[:, g] @ w[g].T + bias[g] for every group in one launch."""
+    _cuda(x, w, bias)
+    G, N, K = w.shape
+    _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.is_contiguous(), "cls_head_gemm: bf16 x, contiguous bf16 w (G, N, K)")
+    M = x.shape[0]
+    x2 = x.reshape(M, G * K)
+    _need(x2.stride(1) == 1, "cls_head_gemm: x rows must be contiguous")
+    if bias is not None:
+        _need(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == G * N, "cls_head_gemm: bias must be f32 (G * N)")
+    out = torch.empty((M, G, N), dtype=torch.bfloat16, device=x.device)
+    rc = _launch("cls_head_gemm", (2.0 * M * G * N * K, float(2 * (x2.numel() + w.numel() + out.numel()))), lambda: lib().pm_cls_head_gemm(
+        x2.data_ptr(), x2.stride(0), K, w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), G * N, N,
+        M, N, K, G, _stream()))
+    check(rc, f"pm_cls_head_gemm(M={M}, N={N}, K={K}, G={G})")
+    return out
+
+
+def cls_attend(x: Tensor, stats: Tensor | None, u: Tensor, scale: float, eps: float) -> Tensor:
+    """pm_cls_attend: x bf16 (N, L, d) (unit last stride), stats f32 (N*L, 2) [mean, rstd] of its rows | None (computed in the
+    kernel with eps), u bf16 (N, H, d) -> ctx bf16 (N, H, d): ctx_h = sum_j softmax_j(scale * rstd_j * (u_h . x_j - mean_j * sum(u_h)))
+    * rstd_j * (x_j - mean_j)."""
+    _cuda(x, stats, u)
+    _need(x.dim() == 3 and u.dim() == 3 and x.dtype == torch.bfloat16 and u.dtype == torch.bfloat16 and x.stride(2) == 1
+          and u.is_contiguous() and u.shape[0] == x.shape[0] and u.shape[2] == x.shape[2], "cls_attend: x (N, L, d), u (N, H, d) bf16")
+    N, L, d = x.shape
+    H = u.shape[1]
+    if stats is not None:
+        _need(stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape == (N * L, 2), "cls_attend: stats must be f32 (N*L, 2)")
+    out = torch.empty((N, H, d), dtype=torch.bfloat16, device=x.device)
+    rc = _launch("cls_attend", (4.0 * N * H * L * d, float(2 * (x.numel() + 2 * u.numel()))), lambda: lib().pm_cls_attend(
+        x.data_ptr(), x.stride(1), x.stride(0), stats.data_ptr() if stats is not None else None, u.data_ptr(), out.data_ptr(),
+        N, L, d, H, float(scale), float(eps), _stream()))
+    check(rc, f"pm_cls_attend(N={N}, L={L}, d={d}, H={H})")
+    return out

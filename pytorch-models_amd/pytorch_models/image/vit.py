@@ -118,14 +118,18 @@ class ViT(nn.Module):
         parts = None
         if imgs.dim() == 4 and imgs.is_cuda and self.patch_embed.weight.dtype == torch.bfloat16:
             parts = self.layers.split_sizes(imgs.shape[0], n_tok, torch.bfloat16, imgs.device)
+        # class-token pooling reads row 0 alone: the encoder returns just that row, and where it can, runs its last layer for
+        # that row only (transformer.py, EncoderLayer.forward_first_row)
+        cls = isinstance(self.pooler, ClassTokenPooling)
         if parts is None:
-            out = self.layers(self.tokens(imgs))
+            out = self.layers(self.tokens(imgs), first_row=cls)
         else:  # a large batch: each part's patch projection runs on the stream its encoder layers run on
-            out = self.layers(producers=[lambda lo=lo, hi=hi: self.tokens(imgs[lo:hi]) for lo, hi in parts], device=imgs.device)
+            out = self.layers(producers=[lambda lo=lo, hi=hi: self.tokens(imgs[lo:hi]) for lo, hi in parts], device=imgs.device,
+                              first_row=cls)
         io = self.patch_embed.weight.dtype  # bf16 model -> bf16 features, fp32 model -> fp32 features
-        if isinstance(self.pooler, ClassTokenPooling):
+        if cls:
             # LayerNorm is row-wise, so normalising only the pooled row equals norm-then-pool (vit.py:83-84)
-            return self.norm(out[:, 0], io)
+            return self.norm(out, io)
         if out.device.type == "cpu":
             return self.pooler(self.norm(out))
         return self.pooler(self.norm(out)).to(io)

@@ -206,6 +206,21 @@ class MHA(nn.Module):
         w, b = self._pack("qkv")
         return derived(self, "pack_qkv_ln", (w, b, norm.weight, norm.bias), lambda: _fold_ln(w, b, norm))
 
+    def _pack_cls(self, norm: "LayerNorm"):
+        """k / v projections with ``norm`` folded in, per head, for a single query (EncoderLayer.forward_first_row):
+        (wku (H, d, hd): u[:, h] = q[:, h] wku[h]^T = W'k,h^T q_h;  wvh (H, hd, d): o[:, h] = ctx[:, h] wvh[h]^T + cv[h];
+        cv (H * hd) = W_v beta + b_v).  The k side's constant (W_k beta + b_k) . q is the same for every key: softmax drops it."""
+        kp, vp = self.k_proj, self.v_proj
+
+        def build():
+            H, hd = self.n_heads, self.head_dim
+            wkl, _, _ = _fold_ln(kp.weight, None, norm)
+            wvl, _, cv = _fold_ln(vp.weight, vp.bias, norm)
+            d = wkl.shape[1]
+            return wkl.view(H, hd, d).transpose(1, 2).contiguous(), wvl.view(H, hd, d).contiguous(), cv
+
+        return derived(self, "pack_cls", (kp.weight, vp.weight, vp.bias, norm.weight, norm.bias), build)
+
     def forward(
         self,
         q: Tensor,
@@ -476,6 +491,46 @@ class EncoderLayer(DecoderLayer):
         return x2.view(*lead, d), ops.ln_stats_finalize(rows, d, next_eps)
 
 
+    # ---- the layer for token 0 only (Encoder.forward(first_row=True) drives this)
+    def first_row_ok(self, x: Tensor) -> bool:
+        """True when forward_first_row serves this layer: a plain pre-norm bf16 layer with plain MHA / MLP (the type tests of
+        chain_ok) in eval mode, head_dim 64, a (batch, tokens, d) bf16 input on a HIP device, geometry pm_cls_attend takes.
+        Never a function of the batch size.  PM_VIT_CLS_TAIL=0 switches it off (the full layer runs, as before)."""
+        sa, mlp = self.sa, self.mlp
+        if os.environ.get("PM_VIT_CLS_TAIL", "1") == "0":
+            return False
+        if not (type(self).forward is EncoderLayer.forward and self.pre_norm and type(sa).forward is MHA.forward
+                and type(sa).attend is MHA.attend and type(mlp).forward is MLP.forward and type(mlp).run is MLP.run
+                and type(self.sa_norm) is LayerNorm and type(self.mlp_norm) is LayerNorm and not self.training):
+            return False
+        if not (x.dim() == 3 and x.is_cuda and x.dtype == torch.bfloat16 and x.stride(2) == 1 and x.shape[1] >= 1
+                and sa.q_proj.weight.is_cuda and sa.q_proj.weight.dtype == torch.bfloat16
+                and mlp.linear1.weight.dtype == torch.bfloat16):
+            return False
+        d = x.shape[2]
+        return (sa.head_dim == 64 and sa.q_proj.in_features == d and sa.k_proj.in_features == d and sa.v_proj.in_features == d
+                and x.stride(1) % 8 == 0 and x.stride(0) % 8 == 0 and ops.cls_attend_supported(x.shape[1], d, sa.n_heads))
+
+    def forward_first_row(self, x: Tensor, stats: Tensor | None, out: Tensor | None = None) -> Tensor:
+        """Row 0 of forward(x) for every sample, (B, L, d) -> (B, d), without the other rows' work.  Everything behind the
+        attention is row-wise; the attention needs one query per sample and head, and with the LayerNorm folded into the k / v
+        weights neither K nor V is projected (csrc/cls_tail.hip): u_h = W'k,h^T q_h scores the stored rows directly, and
+        o_h = W'v,h ctx_h + c_v,h with ctx_h the softmax-weighted sum of the normalised rows.  ``stats`` = (mean, rstd) of the
+        rows of ``x`` under sa_norm from the chain (None: pm_cls_attend computes them in its pass)."""
+        sa, mlp = self.sa, self.mlp
+        B, d = x.shape[0], x.shape[2]
+        x0 = x[:, 0]  # strided rows: the kernels take a row stride
+        q = ops.linear(self.sa_norm(x0), sa.q_proj.weight, _f32(sa.q_proj, "b", sa.q_proj.bias))
+        wku, wvh, cv = sa._pack_cls(self.sa_norm)
+        u = ops.cls_head_gemm(q, wku)
+        ctx = ops.cls_attend(x, stats, u, sa.head_dim ** -0.5, self.sa_norm.eps)
+        o = ops.cls_head_gemm(ctx, wvh, cv).view(B, -1)
+        y = ops.linear(o, sa.out_proj.weight, _f32(sa.out_proj, "b", sa.out_proj.bias), resid=x0)
+        l1, l2 = mlp.linear1, mlp.linear2
+        h = ops.linear(self.mlp_norm(y), l1.weight, _f32(l1, "b", l1.bias), act=mlp.act_name)
+        return ops.linear(h, l2.weight, _f32(l2, "b", l2.bias), resid=y, out=out)
+
+
 class Encoder(nn.Sequential):
     def __init__(
         self,
@@ -495,11 +550,15 @@ class Encoder(nn.Sequential):
             for _ in range(n_layers)
         ])
 
-    def forward(self, x: Tensor | None = None, *, producers=None, device: torch.device | None = None) -> Tensor:
+    def forward(self, x: Tensor | None = None, *, producers=None, device: torch.device | None = None,
+                first_row: bool = False) -> Tensor:
         """The layers in order.  Runs of plain pre-norm layers at GEMM-sized M are chained: each residual GEMM
         (out_proj, linear2) also emits the row statistics of its output, and the next GEMM (q/k/v, linear1)
         applies the LayerNorm in its epilogue - no LayerNorm kernel, no LN(x) round trip through HBM.
-        ``producers`` (instead of x): one callable per batch part (split_sizes), each called on its part's stream."""
+        ``producers`` (instead of x): one callable per batch part (split_sizes), each called on its part's stream.
+        ``first_row`` (opt-in; ViT's class-token pooling): return row 0 of every sample, (B, d), instead of (B, L, d).  Where
+        the last layer's first_row_ok holds, that layer runs for row 0 only (EncoderLayer.forward_first_row) and each part
+        writes its rows straight into the result; otherwise the full layer runs and row 0 is a view of its output."""
         layers = list(self)
         fold = os.environ.get("PM_LN_FOLD", "1") != "0"
 
@@ -517,9 +576,12 @@ class Encoder(nn.Sequential):
             halves = None  # the parts would take different paths (LayerNorm folded / not): keep the batch in one piece
         if halves is None and producers is None:
             ok, stats = plan(x), None
-            for i in range(len(layers)):
+            tail = first_row and bool(layers) and isinstance(layers[-1], EncoderLayer) and layers[-1].first_row_ok(x)
+            for i in range(len(layers) - tail):
                 x, stats = step(i, ok, x, stats)
-            return x
+            if tail:
+                return layers[-1].forward_first_row(x, stats)
+            return x[:, 0] if first_row else x
         # Two halves of the batch on two HIP streams, layer by layer.  Samples are independent and every kernel is
         # batch-position invariant, so the result is bit-identical; what changes is the schedule: the large-M kernels are
         # persistent (one workgroup per CU) and their last round of tiles leaves most CUs idle - 2.31 rounds run as 3 at
@@ -533,8 +595,9 @@ class Encoder(nn.Sequential):
         # then only be handed out while everything the side streams do is still ordered behind it by the wait below; every
         # tensor a side stream allocates also dies on it, so the caching allocator needs no cross-stream bookkeeping.
         out = None
+        tail = first_row and producers is None and bool(layers) and isinstance(layers[-1], EncoderLayer) and all(layers[-1].first_row_ok(h) for h in halves)
         if producers is None:
-            out = torch.empty_like(x)
+            out = x.new_empty((x.shape[0], x.shape[2])) if tail else torch.empty_like(x)
         elif getattr(self, "_pm_out_shape", None) is not None:
             shape, dtype = self._pm_out_shape
             out = torch.empty(shape, dtype=dtype, device=device)
@@ -551,30 +614,37 @@ class Encoder(nn.Sequential):
         first = [0]
         for t, _ in state:
             first.append(first[-1] + t.shape[0])
-        want = ((first[-1],) + tuple(state[0][0].shape[1:]), state[0][0].dtype)
+        mixed = any(o != oks[0] for o in oks[1:])  # (producers only; rare) the parts would take different paths
+        if producers is not None:
+            tail = first_row and not mixed and bool(layers) and isinstance(layers[-1], EncoderLayer) and all(layers[-1].first_row_ok(t) for t, _ in state)
+        want = ((first[-1],) + tuple(state[0][0].shape[2 if tail else 1:]), state[0][0].dtype)
         if out is None or (tuple(out.shape), out.dtype) != want:  # (producers: the shape is known once the first part exists)
             out = torch.empty(want[0], dtype=want[1], device=device)
             for st in streams[1:]:  # allocated behind the fork this once: order the side streams behind the allocation
                 st.wait_stream(cur)
         if producers is not None:
             self._pm_out_shape = want  # the next call with this geometry allocates in front of the fork
-        if any(o != oks[0] for o in oks[1:]):  # (producers only; rare) different paths per part: one piece on the caller's stream
+        if mixed:  # one piece on the caller's stream
             for k in range(n_parts):
                 with torch.cuda.stream(streams[k]):
                     out[first[k] : first[k + 1]].copy_(state[k][0])
             for st in streams[1:]:
                 cur.wait_stream(st)
-            return self.forward(out)
+            return self.forward(out, first_row=first_row)
         for i in range(len(layers)):
             for k in reversed(range(n_parts)):
                 with torch.cuda.stream(streams[k]):
+                    if tail and i == len(layers) - 1:  # each part writes its (B_part, d) rows straight into the result
+                        layers[i].forward_first_row(state[k][0], state[k][1], out=out[first[k] : first[k + 1]])
+                        state[k] = None
+                        continue
                     state[k] = step(i, oks[k], state[k][0], state[k][1])
                     if i == len(layers) - 1:
                         out[first[k] : first[k + 1]].copy_(state[k][0])
                         state[k] = None
         for st in streams[1:]:
             cur.wait_stream(st)
-        return out
+        return out[:, 0] if first_row and not tail else out
 
     def split_sizes(self, batch: int, tokens: int, dtype: torch.dtype, device: torch.device):
         """[(lo, hi), ...] = the batch ranges forward() would run on separate streams for a (batch, tokens, d) input, or None."""
