@@ -379,6 +379,35 @@ int pm_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_tile
                       int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot, float* margin_out, const void* emb,
                       const float* pos, float* x, int64_t d, int64_t V, int32_t* ticket, int64_t B, void* stream);
 
+/* Beam search on top of the decode step (csrc/decode_beam.hip; DESIGN.md "Beam search"): rows r = b * W + w (clip b, beam w),
+ * 1 <= W <= 8, the step runs at B * W rows in full-logit mode and ends with these three launches instead of a token choice.
+ * The reference follows one hypothesis per sequence (text/generator.py:23-35) and decodes nothing for Whisper (README.md:86).
+ *
+ * pm_dec_beam_topw: per row the log-sum-exp of logits[r, :V] (f32, row stride ldl; -inf entries allowed) and its W largest
+ * logits (ties: lowest index first) as candidates cand_score[r, k] = scores[r] + (logit - lse), cand_tok[r, k] (int32).  A row
+ * with finished[r] != 0 (and eos >= 0) offers (scores[r], eos) alone, its other entries carry token -1; a row at -inf offers
+ * tokens 0 .. W - 1 at -inf.  Nothing happens while *pos_ptr + 1 < P (the prompt is being forced).  eos < 0: no row finishes. */
+int pm_dec_beam_topw(const float* logits, int64_t ldl, int64_t V, int64_t W, const float* scores, const int32_t* finished,
+                     int64_t eos, const int32_t* pos_ptr, int64_t P, float* cand_score, int32_t* cand_tok, int64_t rows,
+                     void* stream);
+
+/* pm_dec_beam_select: per clip the W best of its W x W candidates, best first (score descending, then lower parent beam, then
+ * lower token id) -> parents[b, j] (int32), scores[b, j], finished[b, j] = the parent's flag or token == eos; the token
+ * histories tokens[b, j, 0..t] = tokens[b, parent_j, 0..t] (int64 (B * W, Ttot), in place) and tokens[b, j, t + 1] = the new
+ * token; then the tail of pm_dec_next_token: tok_cur, x[r] = emb[token] + pos[t + 1], ticketed advance of *pos_ptr.  While
+ * t + 1 < P: identity parents, the token is prompt[r, t + 1] (prompt: int64 (B * W, P)), scores and flags stay. */
+int pm_dec_beam_select(const float* cand_score, const int32_t* cand_tok, int64_t W, float* scores, int32_t* finished,
+                       int32_t* parents, int64_t eos, int64_t* tokens, int64_t Ttot, int32_t* pos_ptr, const int64_t* prompt,
+                       int64_t P, int64_t* tok_cur, const void* emb, const float* pos, float* x, int64_t d, int64_t V,
+                       int32_t* ticket, int64_t B, void* stream);
+
+/* pm_dec_beam_reorder: for each of the n_caches device pointers in table (uint64 each: the K and V self-attention caches of every
+ * layer, (B * W, H, Tmax, 64) bf16, or f32 with kv_f32), cache[b, j, h, 0..t, :] = cache[b, parents[b, j], h, 0..t, :], in place
+ * and bit for bit, t = *pos_ptr - 1 (it runs after pm_dec_beam_select moved the position); positions above t are not written;
+ * clips with identity parents are left alone. */
+int pm_dec_beam_reorder(const void* table, int64_t n_caches, const int32_t* parents, const int32_t* pos_ptr, int64_t B, int64_t W,
+                        int64_t H, int64_t Tmax, int kv_f32, void* stream);
+
 /* ConvNeXt (reference: pytorch_models/image/convnext.py), csrc/convnext.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype
  * PM_BF16 or PM_F32; gamma / beta / bias f32.  The pointwise MLP and the downsample's Conv2d(C, 2C, 2, 2) run on the GEMMs above.
  *

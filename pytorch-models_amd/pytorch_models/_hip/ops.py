@@ -701,6 +701,86 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
     return logits
 
 
+def _beam_state(what: str, W: int, **named: Tensor) -> int:
+    """the (B, W) state tensors of the beam ops: contiguous, one shape; returns B"""
+    shape = None
+    for name, (t, dt) in named.items():
+        _need(t.dim() == 2 and t.shape[1] == W and t.dtype == dt and t.is_contiguous() and (shape is None or t.shape == shape),
+              f"{what}: {name} must be {dt} (B, W) contiguous")
+        shape = t.shape
+    return shape[0]
+
+
+def dec_beam_topw(logits: Tensor, scores: Tensor, finished: Tensor, pos: Tensor, P: int, eos: int | None):
+    """pm_dec_beam_topw as a standalone op: logits (B * W, V) f32, scores (B, W) f32, finished (B, W) int32 ->
+    (cand_score (B * W, W) f32, cand_tok (B * W, W) int32)."""
+    _cuda(logits, scores, finished, pos)
+    W = scores.shape[-1]
+    B = _beam_state("dec_beam_topw", W, scores=(scores, torch.float32), finished=(finished, torch.int32))
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == B * W,
+          "dec_beam_topw: logits f32 (B * W, V)")
+    _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_beam_topw: pos is one device int32")
+    V = logits.shape[1]
+    cs = torch.empty(B * W, W, dtype=torch.float32, device=logits.device)
+    ct = torch.empty(B * W, W, dtype=torch.int32, device=logits.device)
+    rc = lib().pm_dec_beam_topw(logits.data_ptr(), logits.stride(0), V, W, scores.data_ptr(), finished.data_ptr(),
+                                -1 if eos is None else eos, pos.data_ptr(), P, cs.data_ptr(), ct.data_ptr(), B * W, _stream())
+    check(rc, f"pm_dec_beam_topw(rows={B * W}, V={V}, W={W})")
+    return cs, ct
+
+
+def dec_beam_select(cand_score: Tensor, cand_tok: Tensor, scores: Tensor, finished: Tensor, parents: Tensor, tokens: Tensor,
+                    pos: Tensor, prompt: Tensor, tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, x: Tensor, ticket: Tensor,
+                    eos: int | None) -> None:
+    """pm_dec_beam_select as a standalone op; scores / finished / parents (B, W), tokens (B * W, Ttot) int64, tok_cur (B * W) and
+    x (B * W, d) f32 are updated IN PLACE and *pos advances by one."""
+    _cuda(cand_score, cand_tok, scores, finished, parents, tokens, pos, prompt, tok_cur, emb, pos_tab, x, ticket)
+    W = scores.shape[-1]
+    B = _beam_state("dec_beam_select", W, scores=(scores, torch.float32), finished=(finished, torch.int32),
+                    parents=(parents, torch.int32))
+    R = B * W
+    _need(cand_score.shape == (R, W) and cand_score.dtype == torch.float32 and cand_score.is_contiguous()
+          and cand_tok.shape == (R, W) and cand_tok.dtype == torch.int32 and cand_tok.is_contiguous(),
+          "dec_beam_select: candidates (B * W, W) f32 / int32")
+    _need(tokens.dim() == 2 and tokens.shape[0] == R and tokens.dtype == torch.int64 and tokens.is_contiguous()
+          and prompt.dim() == 2 and prompt.shape[0] == R and prompt.dtype == torch.int64 and prompt.is_contiguous()
+          and tokens.shape[1] >= prompt.shape[1] and tok_cur.shape == (R,) and tok_cur.dtype == torch.int64,
+          "dec_beam_select: tokens (B * W, Ttot), prompt (B * W, P), tok_cur (B * W) int64")
+    V, d = emb.shape
+    _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
+          and pos_tab.shape[1] == d and pos_tab.shape[0] >= tokens.shape[1] and x.shape == (R, d) and x.dtype == torch.float32
+          and x.is_contiguous(), "dec_beam_select: emb bf16 (V, d), pos f32 (>= Ttot, d), x f32 (B * W, d)")
+    _need(pos.dtype == torch.int32 and pos.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1,
+          "dec_beam_select: pos and ticket are one device int32 each")
+    rc = lib().pm_dec_beam_select(cand_score.data_ptr(), cand_tok.data_ptr(), W, scores.data_ptr(), finished.data_ptr(),
+                                  parents.data_ptr(), -1 if eos is None else eos, tokens.data_ptr(), tokens.shape[1], pos.data_ptr(),
+                                  prompt.data_ptr(), prompt.shape[1], tok_cur.data_ptr(), emb.data_ptr(), pos_tab.data_ptr(),
+                                  x.data_ptr(), d, V, ticket.data_ptr(), B, _stream())
+    check(rc, f"pm_dec_beam_select(B={B}, W={W})")
+
+
+def dec_beam_reorder(caches: list[Tensor], parents: Tensor, pos: Tensor) -> None:
+    """pm_dec_beam_reorder as a standalone op: every cache (B * W, H, Tmax, 64) (all bf16 or all f32, one geometry) is re-gathered
+    IN PLACE, rows 0 .. pos - 1 of row (b, j) from row (b, parents[b, j])."""
+    _cuda(parents, pos, *caches)
+    B, W = parents.shape
+    _need(parents.dtype == torch.int32 and parents.is_contiguous(), "dec_beam_reorder: parents int32 (B, W)")
+    _need(bool(((parents >= 0) & (parents < W)).all()), "dec_beam_reorder: parents outside 0 .. W - 1")
+    _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_beam_reorder: pos is one device int32")
+    c0 = caches[0]
+    _need(c0.dim() == 4 and c0.shape[0] == B * W and c0.shape[3] == 64 and c0.dtype in (torch.bfloat16, torch.float32),
+          "dec_beam_reorder: caches (B * W, H, Tmax, 64) bf16 or f32")
+    _need(int(pos.item()) <= c0.shape[2], "dec_beam_reorder: position beyond the caches")
+    for c in caches:
+        _need(c.shape == c0.shape and c.dtype == c0.dtype and c.is_contiguous() and c.data_ptr() % 16 == 0,
+              "dec_beam_reorder: caches of one geometry, contiguous, 16-byte aligned")
+    table = torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64, device=c0.device)
+    rc = lib().pm_dec_beam_reorder(table.data_ptr(), len(caches), parents.data_ptr(), pos.data_ptr(), B, W, c0.shape[1], c0.shape[2],
+                                   int(c0.dtype == torch.float32), _stream())
+    check(rc, f"pm_dec_beam_reorder(B={B}, W={W}, caches={len(caches)})")
+    torch.cuda.current_stream().synchronize()  # the pointer table must outlive the launch
+
+
 # ------------------------------------------------------------------------------------------------ ConvNeXt (csrc/convnext.hip)
 def _f32vec(t: Tensor, n: int, what: str) -> None:
     _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, f"{what} must be f32 ({n})")

@@ -46,14 +46,29 @@ class WhisperRules:
 
 class GreedyDecoder:
     """State + launch list of the decode step for one (decoder, batch, memory length) geometry."""
+    _beam = False  # BeamDecoder: rows = sequences x beams, the step ends in the beam kernels
 
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
-                 topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False) -> None:
+                 topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
+                 beams: int = 1, eos: int | None = None) -> None:
         """``kv32``: the reference-accuracy form of the same step - fp32 memory in, cross and self K/V kept in fp32 (nothing is
         rounded when it is cached; pm_dec_attention_fused_kv32), everything else as in the throughput path, whose projections
-        are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it."""
+        are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it.
+        ``beams`` > 1 (through BeamDecoder): the same step at B * beams rows (row b * beams + w) in full-logit mode, ending in
+        the beam kernels instead of a token choice; ``beams`` = 1 builds exactly the launch list it always did."""
         if path not in ("auto", "launches", "persistent"):
             raise ValueError("greedy decode: path must be 'auto', 'launches' or 'persistent'")
+        W = int(beams)
+        if not self._beam and W != 1:
+            raise ValueError("greedy decode: beams > 1 is BeamDecoder's")
+        if self._beam:
+            if not 1 <= W <= 8:
+                raise ValueError("beam decode: beams must be in 1..8")
+            if path == "persistent":
+                raise NotImplementedError("beam decode: the persistent layer kernel follows one hypothesis per sequence (path='launches')")
+            if topk != 1 or margins:
+                raise ValueError("beam decode: topk sampling and arg-max margins are greedy decode's")
+            path = "launches"
         E = dec.token_embs.weight
         if E.dtype != torch.bfloat16 or not E.is_cuda:
             raise NotImplementedError("greedy decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda())")
@@ -67,6 +82,16 @@ class GreedyDecoder:
         if prompt.shape[0] != B or prompt.dtype != torch.int64 or P < 1:
             raise ValueError("greedy decode: prompt must be int64 (B, P >= 1)")
         V = E.shape[0]
+        self.clips, self.W = B, W
+        if self._beam:  # every buffer and launch below is per ROW
+            if B * W > 64:
+                raise NotImplementedError("beam decode: at most 64 rows (sequences x beams) per call (shard larger batches)")
+            if W > V:
+                raise ValueError("beam decode: more beams than vocabulary entries")
+            if kv32 and B * W * dec.layers[0].sa.n_heads > 256:
+                raise NotImplementedError("beam decode: fp32 K/V caches run on the fused attention blocks (B * beams * n_heads <= 256)")
+            prompt = prompt.repeat_interleave(W, 0)
+            B *= W
         if int(prompt.min()) < 0 or int(prompt.max()) >= V:
             raise ValueError("greedy decode: prompt ids out of range")
         self.Ttot = P + n_new
@@ -134,7 +159,7 @@ class GreedyDecoder:
         self.ws_val = torch.empty(B, n_tiles, **f32)
         self.ws_idx = torch.empty(B, n_tiles, dtype=torch.int32, device=dev)
         pos_f32 = _f32(dec, "pos", dec.pos_embs)
-        mem2 = memory.reshape(B * S, d) if memory is not None else None
+        mem2 = memory.reshape(self.clips * S, d) if memory is not None else None
         self._keep = [E, pos_f32, memory]  # tensors the launch list points into
         self.launches = []  # (fn, args): raw pointers only -> the loop has no per-step Python work beyond ctypes
 
@@ -321,7 +346,7 @@ class GreedyDecoder:
             add(L.pm_layernorm, cur.data_ptr(), d, 1, g.data_ptr(), b.data_ptr(), float(dec.norm.eps), self.xn.data_ptr(), d, 1,
                 B, d, None)
             xl, gl, bl = self.xn, None, None
-        if topk == 1 and rules is None:
+        if topk == 1 and rules is None and not self._beam:
             dec_linear(xl, d, gl, bl, dec.norm.eps, E, None, None, None, V, mode=2, ldo=0)
             # token choice + the next step's embedding row + position advance: one launch
             add(L.pm_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), n_tiles, self.pos.data_ptr(),
@@ -342,6 +367,8 @@ class GreedyDecoder:
                     self.pos.data_ptr(), P, rules.eot, rules.no_timestamps, rules.timestamp_begin, rules.max_initial_timestamp,
                     sup.data_ptr() if sup.numel() else None, sup.numel(), blk.data_ptr() if blk.numel() else None, blk.numel(),
                     B, None)
+            if self._beam:
+                return self._beam_tail(add, L, E, pos_f32, rules, eos, V, d, H, Tmax)
             add(L.pm_dec_sample_topk, self.logits.data_ptr(), self.logits.stride(0), V, topk, int(seed) & (2**64 - 1),
                 self.pos.data_ptr(), self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot,
                 E.data_ptr(), pos_f32.data_ptr(), self.x.data_ptr(), d, self.ticket.data_ptr(), B, None)
@@ -359,15 +386,15 @@ class GreedyDecoder:
     def rebind(self, memory: Tensor, prompt: Tensor) -> None:
         """New clips, same geometry: re-project the cross K/V INTO the existing buffers and swap the prompt, so the
         captured graph (which holds raw pointers) stays valid."""
-        assert (self.B, self.P) == tuple(prompt.shape)
+        assert (self.clips, self.P) == tuple(prompt.shape)
         if memory is not None:
             B, S, d = memory.shape
-            assert B == self.B and memory.dtype == (torch.float32 if self.kv32 else torch.bfloat16)
+            assert B == self.clips and memory.dtype == (torch.float32 if self.kv32 else torch.bfloat16)
             mem2 = memory.reshape(B * S, d)
             for kv, (wkv, bkv) in zip(self.cross_kv, self._cross_w):
-                assert kv.shape[0] == B * S
+                assert kv.shape[0] == self.B * S
                 self._project_memory(mem2, wkv, bkv, out=kv)
-        self.prompt.copy_(prompt)
+        self.prompt.copy_(prompt if self.W == 1 else prompt.repeat_interleave(self.W, 0))
         self.tokens[:, : self.P] = self.prompt
 
     def step(self, log: dict | None = None) -> None:
@@ -421,6 +448,80 @@ class GreedyDecoder:
             raise RuntimeError("greedy decode: a hand-off of the persistent decode-step kernel timed out (not every workgroup of "
                                "the launch was resident, or the device is shared); tokens of this run are invalid - re-run with "
                                "path='launches'")
+
+
+class BeamDecoder(GreedyDecoder):
+    """Fixed-shape beam search of width ``beams`` over B clips: GreedyDecoder's step at B * beams rows (row b * beams + w) in
+    full-logit mode, then pm_dec_whisper_rules (optional), pm_dec_beam_topw, pm_dec_beam_select, pm_dec_beam_reorder - captured
+    and replayed like the greedy step; parents, scores and the K/V re-gather never leave the device (DESIGN.md "Beam search").
+    State: ``scores`` (B, W) f32, ``finished`` / ``parents`` (B, W) int32 (of the last step), ``tokens`` (B * W, P + n) int64,
+    ``logits`` (B * W, V) f32 of the last step (after the rules), ``self_k`` / ``self_v`` per layer (B * W, H, P + n, 64)."""
+    _beam = True
+
+    def __init__(self, dec, memory: Tensor | None, prompt: Tensor, n_new: int, beams: int, *, eos: int | None = None,
+                 rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False, fused: bool = True) -> None:
+        super().__init__(dec, memory, prompt, n_new, False, fused, 1, 0, rules, path, kv32, beams=beams, eos=eos)
+
+    def _beam_tail(self, add, L, E, pos_f32, rules, eos, V, d, H, Tmax) -> None:
+        dev, B, W = E.device, self.clips, self.W
+        if eos is None and rules is not None:
+            eos = rules.eot
+        if eos is not None and not 0 <= int(eos) < V:
+            raise ValueError("beam decode: eos_token_id outside the vocabulary")
+        self.eos = -1 if eos is None else int(eos)
+        self.scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+        self.finished = torch.zeros(B, W, dtype=torch.int32, device=dev)
+        self.parents = torch.zeros(B, W, dtype=torch.int32, device=dev)
+        self._cand_score = torch.empty(B * W, W, dtype=torch.float32, device=dev)
+        self._cand_tok = torch.zeros(B * W, W, dtype=torch.int32, device=dev)
+        # the layers' (K, V) cache pointers, read by the one reorder launch
+        self._cache_table = torch.tensor([c.data_ptr() for kv in zip(self.self_k, self.self_v) for c in kv], dtype=torch.int64,
+                                         device=dev)
+        add(L.pm_dec_beam_topw, self.logits.data_ptr(), self.logits.stride(0), V, W, self.scores.data_ptr(),
+            self.finished.data_ptr(), self.eos, self.pos.data_ptr(), self.P, self._cand_score.data_ptr(),
+            self._cand_tok.data_ptr(), B * W, None)
+        add(L.pm_dec_beam_select, self._cand_score.data_ptr(), self._cand_tok.data_ptr(), W, self.scores.data_ptr(),
+            self.finished.data_ptr(), self.parents.data_ptr(), self.eos, self.tokens.data_ptr(), self.Ttot, self.pos.data_ptr(),
+            self.prompt.data_ptr(), self.P, self.tok_cur.data_ptr(), E.data_ptr(), pos_f32.data_ptr(), self.x.data_ptr(), d, V,
+            self.ticket.data_ptr(), B, None)
+        add(L.pm_dec_beam_reorder, self._cache_table.data_ptr(), self._cache_table.numel(), self.parents.data_ptr(),
+            self.pos.data_ptr(), B, W, H, Tmax, int(self.kv32), None)
+
+    def _project_memory(self, mem2: Tensor, wkv: Tensor, bkv, out: Tensor | None = None) -> Tensor:
+        """cross K/V projected ONCE per clip, then copied to the clip's W rows (the attention blocks read one K/V image per row;
+        sharing one between a clip's beams needs attention kernels of its own: DESIGN.md)."""
+        kv = super()._project_memory(mem2, wkv, bkv)
+        S = mem2.shape[0] // self.clips
+        rows = kv.view(self.clips, 1, S, kv.shape[1]).expand(-1, self.W, -1, -1)
+        if out is None:
+            return rows.reshape(self.clips * self.W * S, kv.shape[1])
+        out.view(self.clips, self.W, S, kv.shape[1]).copy_(rows)
+        return out
+
+    def reset(self) -> None:
+        super().reset()
+        self.scores.fill_(float("-inf"))  # only beam 0 is live at the first generated position: W distinct continuations
+        self.scores[:, 0] = 0.0
+        self.finished.zero_()
+        self.parents.copy_(torch.arange(self.W, dtype=torch.int32, device=self.parents.device).expand_as(self.parents))
+
+    def beams(self) -> tuple[Tensor, Tensor]:
+        """(tokens (B, W, P + n) int64, scores (B, W) f32), best beam first"""
+        return self.tokens.view(self.clips, self.W, self.Ttot), self.scores
+
+
+@torch.no_grad()
+def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams: int, eos_token_id: int | None = None,
+                graph: bool = True, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
+                return_beams: bool = False):
+    """Beam search of width ``beams`` (1..8, B * beams <= 64): the best hypothesis per sequence, (B, P + n_new) int64, or with
+    ``return_beams`` (tokens (B, beams, P + n_new), scores (B, beams) f32 = sum of the tokens' log-probabilities), best first.
+    No length penalty, no early exit: always n_new steps; a hypothesis that emitted ``eos_token_id`` (default: rules.eot when
+    rules are given, else none) is extended with it at no cost."""
+    st = BeamDecoder(dec, memory, prompt, n_new, beams, eos=eos_token_id, rules=rules, path=path, kv32=kv32)
+    st.run(graph)
+    toks, scores = st.beams()
+    return (toks.clone(), scores.clone()) if return_beams else toks[:, 0].clone()
 
 
 @torch.no_grad()
