@@ -8,7 +8,7 @@ import os
 import torch
 from torch import Tensor
 
-from . import ACT, PM_BF16, PM_F32, check, lib
+from . import ACT, PM_BF16, PM_F32, check, decode_plan as plan, lib
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -615,7 +615,8 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
     return out
 
 
-# ---- decode-step kernels as standalone ops (the generator builds raw launch lists; these wrappers serve tests) ----
+# ---- decode-step kernels as standalone ops (the decoders build their launch lists in decode_plan.py, whose argument builders
+# these wrappers share; the wrappers serve tests) ----
 def dec_linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, ln: tuple | None = None, act: str = "none",
                resid: Tensor | None = None) -> Tensor:
     """y = act(LN?(x) @ w.T + bias) + resid for <= 64 rows of f32 x and bf16 w (fp32-exact: bf16x3 split)."""
@@ -624,13 +625,8 @@ def dec_linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, ln: tuple | 
     M, K = x.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    g, b, eps = ln if ln is not None else (None, None, 0.0)
-    rc = lib().pm_dec_linear(x.data_ptr(), x.stride(0), g.data_ptr() if g is not None else None,
-                             b.data_ptr() if b is not None else None, float(eps), w.data_ptr(), w.stride(0),
-                             bias.data_ptr() if bias is not None else None, resid.data_ptr() if resid is not None else None,
-                             resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0), M, N, K, ACT[act], 0,
-                             None, None, 0, 0, 0, None, None, None, _stream())
-    check(rc, f"pm_dec_linear(M={M}, N={N}, K={K})")
+    plan.call(lib().pm_dec_linear, plan.linear_args(x, w, out, M, ln=ln, bias=bias, resid=resid, act=ACT[act]), _stream(),
+              f"pm_dec_linear(M={M}, N={N}, K={K})")
     return out
 
 
@@ -642,14 +638,9 @@ def dec_linear_ksplit(x: Tensor, w: Tensor, bias: Tensor | None = None, *, k_spl
     M, K = x.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    nt, mt = (N + 15) // 16, (M + 15) // 16
-    mt = 1 if mt <= 1 else 2 if mt == 2 else 4  # row tiles of the kernel instantiation
-    ws = torch.empty(nt * k_split * mt * 256, dtype=torch.float32, device=x.device)
-    cnt = torch.zeros(nt * 4, dtype=torch.int32, device=x.device)  # one ticket per (feature tile, row tile)
-    rc = lib().pm_dec_linear_ksplit(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
-                                    resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0,
-                                    out.data_ptr(), out.stride(0), M, N, K, ACT[act], k_split, ws.data_ptr(), cnt.data_ptr(), _stream())
-    check(rc, f"pm_dec_linear_ksplit(M={M}, N={N}, K={K}, k_split={k_split})")
+    ws, cnt = plan.ksplit_workspace(M, N, k_split, x.device)
+    plan.call(lib().pm_dec_linear_ksplit, plan.ksplit_args(x, w, out, M, k_split, ws, cnt, bias=bias, resid=resid, act=ACT[act]),
+              _stream(), f"pm_dec_linear_ksplit(M={M}, N={N}, K={K}, k_split={k_split})")
     _need(int(cnt.abs().sum()) == 0, "pm_dec_linear_ksplit left a ticket counter non-zero")
     return out
 
@@ -662,10 +653,7 @@ def dec_argmax(x: Tensor, w: Tensor, ln: tuple) -> tuple[Tensor, Tensor]:
     nt = (N + tile - 1) // tile
     wv = torch.empty(M, nt, dtype=torch.float32, device=x.device)
     wi = torch.empty(M, nt, dtype=torch.int32, device=x.device)
-    g, b, eps = ln
-    rc = lib().pm_dec_linear(x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(), float(eps), w.data_ptr(), w.stride(0), None,
-                             None, 0, None, 0, M, N, K, 0, 2, None, None, 0, 0, 0, None, wv.data_ptr(), wi.data_ptr(), _stream())
-    check(rc, "pm_dec_linear(argmax)")
+    plan.call(lib().pm_dec_linear, plan.linear_args(x, w, None, M, ln=ln, mode=2, argmax_ws=(wv, wi)), _stream(), "pm_dec_linear(argmax)")
     best = wv.max(1)
     cand = torch.where(wv == best.values[:, None], wi, torch.full_like(wi, 2**31 - 1))
     return cand.min(1).values.long(), best.values
@@ -676,9 +664,7 @@ def dec_attention(q: Tensor, k: Tensor, v: Tensor, lk: int) -> Tensor:
     _cuda(q, k, v)
     B, H, T, _ = k.shape
     out = torch.empty_like(q)
-    rc = lib().pm_dec_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), k.stride(1), k.stride(2), None, lk, T,
-                                out.data_ptr(), B, H, _stream())
-    check(rc, "pm_dec_attention")
+    plan.call(lib().pm_dec_attention, plan.attention_args(q, plan.cache_kv(k, v), out, B, H, pos=None, lk_add=lk, lk_max=T), _stream())
     return out
 
 

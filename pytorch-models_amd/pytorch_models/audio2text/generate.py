@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 from torch import Tensor
 
-from .._hip import DecLayer, check, lib, ops
+from .._hip import DecLayer, decode_plan as plan, lib, ops
 from ..transformer import _f32
 
 
@@ -27,8 +27,9 @@ from ..transformer import _f32
 PERSISTENT_BY_DEFAULT = False
 
 
-def _ptr(t: Tensor | None):
-    return None if t is None else t.data_ptr()
+def _ln(norm) -> tuple:
+    """(gamma f32, beta f32, eps) of a LayerNorm module"""
+    return _f32(norm, "g", norm.weight), _f32(norm, "b", norm.bias), norm.eps
 
 
 @dataclass
@@ -44,9 +45,8 @@ class WhisperRules:
     blank: tuple = ()
 
 
-class GreedyDecoder:
+class GreedyDecoder(plan.CapturedStep):
     """State + launch list of the decode step for one (decoder, batch, memory length) geometry."""
-    _beam = False  # BeamDecoder: rows = sequences x beams, the step ends in the beam kernels
 
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
                  topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
@@ -58,17 +58,44 @@ class GreedyDecoder:
         the beam kernels instead of a token choice; ``beams`` = 1 builds exactly the launch list it always did."""
         if path not in ("auto", "launches", "persistent"):
             raise ValueError("greedy decode: path must be 'auto', 'launches' or 'persistent'")
-        W = int(beams)
-        if not self._beam and W != 1:
+        self.W = int(beams)
+        path = self._check_request(path, topk, margins)
+        prompt = self._check_geometry(dec, memory, prompt, n_new, kv32)
+        self._choose_path(dec, path, fused)
+        self._choose_attention(memory, fused, kv32)
+        # plain projections with a long K (fc2: K = 4 d) are split over workgroups along K: see pm_dec_linear_ksplit
+        super().__init__(self.B, self._E.device, k_split=int(os.environ.get("PM_DEC_KSPLIT", "4")),
+                         ksplit_min_k=int(os.environ.get("PM_DEC_KSPLIT_MINK", "1024")))
+        self._allocate(dec, memory, prompt, margins)
+        for layer in dec.layers:
+            if not layer.pre_norm:
+                raise NotImplementedError("greedy decode: pre-norm layers only (the post-norm GPT decodes through forward())")
+            if (layer.ca is None) != (memory is None):
+                raise ValueError("greedy decode: cross-attention layers need a memory, decoder-only layers must not get one")
+            self._self_block(layer)
+            if layer.ca is not None:
+                self._cross_block(layer, memory.reshape(self.clips * self.S, self.d))
+            self._mlp_block(layer, last=layer is dec.layers[-1])
+        self.err = torch.zeros(1, dtype=torch.int32, device=self._E.device)
+        if self.path == "persistent":
+            self._persistent_table(dec)
+        if not 1 <= topk <= 64:
+            raise ValueError("greedy decode: topk must be in 1..64")
+        self.topk = topk
+        self._token_tail(dec, topk, seed, rules, margins, eos)
+
+    # ---- what is asked for
+    def _check_request(self, path: str, topk: int, margins: bool) -> str:
+        if self.W != 1:
             raise ValueError("greedy decode: beams > 1 is BeamDecoder's")
-        if self._beam:
-            if not 1 <= W <= 8:
-                raise ValueError("beam decode: beams must be in 1..8")
-            if path == "persistent":
-                raise NotImplementedError("beam decode: the persistent layer kernel follows one hypothesis per sequence (path='launches')")
-            if topk != 1 or margins:
-                raise ValueError("beam decode: topk sampling and arg-max margins are greedy decode's")
-            path = "launches"
+        return path
+
+    def _rows(self, dec, prompt: Tensor, kv32: bool) -> Tensor:
+        """the prompt of every ROW of the step (BeamDecoder: sequences x beams)"""
+        return prompt
+
+    def _check_geometry(self, dec, memory, prompt: Tensor, n_new: int, kv32: bool) -> Tensor:
+        """validates; sets clips, B (rows), S, d, V, P, H, inner, Ttot, n_steps; returns the rows' prompt"""
         E = dec.token_embs.weight
         if E.dtype != torch.bfloat16 or not E.is_cuda:
             raise NotImplementedError("greedy decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda())")
@@ -82,16 +109,9 @@ class GreedyDecoder:
         if prompt.shape[0] != B or prompt.dtype != torch.int64 or P < 1:
             raise ValueError("greedy decode: prompt must be int64 (B, P >= 1)")
         V = E.shape[0]
-        self.clips, self.W = B, W
-        if self._beam:  # every buffer and launch below is per ROW
-            if B * W > 64:
-                raise NotImplementedError("beam decode: at most 64 rows (sequences x beams) per call (shard larger batches)")
-            if W > V:
-                raise ValueError("beam decode: more beams than vocabulary entries")
-            if kv32 and B * W * dec.layers[0].sa.n_heads > 256:
-                raise NotImplementedError("beam decode: fp32 K/V caches run on the fused attention blocks (B * beams * n_heads <= 256)")
-            prompt = prompt.repeat_interleave(W, 0)
-            B *= W
+        self._E, self.clips, self.S, self.d, self.V, self.P = E, B, S, d, V, P
+        prompt = self._rows(dec, prompt, kv32)  # every buffer and launch below is per ROW
+        B = prompt.shape[0]
         if int(prompt.min()) < 0 or int(prompt.max()) >= V:
             raise ValueError("greedy decode: prompt ids out of range")
         self.Ttot = P + n_new
@@ -99,25 +119,27 @@ class GreedyDecoder:
             raise ValueError(f"greedy decode: {self.Ttot} positions > max_seq_len {dec.pos_embs.shape[0]}")
         if B > 64:
             raise NotImplementedError("greedy decode: at most 64 sequences per call (shard larger batches)")
-        dev = E.device
         ops.check_devices(E, memory, prompt if prompt.is_cuda else None)
         H = dec.layers[0].sa.n_heads
-        inner = H * 64
         for i, layer in enumerate(dec.layers):  # the launch list below is built per layer from ONE geometry
             for name, att in (("sa", layer.sa), ("ca", layer.ca)):
                 if att is not None and (att.head_dim != 64 or att.n_heads != H or att.n_heads * 64 != d):
                     raise NotImplementedError(f"greedy decode: layer {i} {name}: head_dim 64 with n_heads * 64 == d_model in every "
                                               f"layer only (got {att.n_heads} x {att.head_dim}, d_model {d})")
-        hid_max = max(layer.mlp.linear1.out_features for layer in dec.layers)
-        # One persistent launch for all layers of a step (csrc/decode_persist.hip) where its geometry rules hold; the
-        # launch-per-stage list otherwise (and on request: tests compare the two)
-        L = lib()
+        self.B, self.H, self.inner, self.n_steps = B, H, H * 64, self.Ttot - 1
+        return prompt
+
+    def _choose_path(self, dec, path: str, fused: bool) -> None:
+        """One persistent launch for all layers of a step (csrc/decode_persist.hip) where its geometry rules hold; the
+        launch-per-stage list otherwise (and on request: tests compare the two)"""
+        d, L = self.d, lib()
+        self._hid_max = hid_max = max(layer.mlp.linear1.out_features for layer in dec.layers)
         nstep = 4 if d <= 512 else 8 if d <= 1024 else 10
-        ksp_p = -(-(hid_max // 32) // (4 * nstep))
+        self._ksp_p = ksp_p = -(-(hid_max // 32) // (4 * nstep))
         acts = {layer.mlp.act_name for layer in dec.layers}
         hids = {layer.mlp.linear1.out_features for layer in dec.layers}
         persist_ok = (all(layer.pre_norm for layer in dec.layers) and len(acts) == 1 and len(hids) == 1 and d % 64 == 0 and d <= 1280
-                      and hid_max % 32 == 0 and ksp_p <= 8 and S <= 2048 and self.Ttot <= 2048 and fused
+                      and hid_max % 32 == 0 and ksp_p <= 8 and self.S <= 2048 and self.Ttot <= 2048 and fused
                       and len({layer.ca is None for layer in dec.layers}) == 1 and hasattr(L, "pm_dec_layers")
                       and L.pm_dec_layers_grid() > 0)
         if path == "persistent" and not persist_ok:
@@ -127,251 +149,220 @@ class GreedyDecoder:
         if path == "auto" and env_path in ("launches", "persistent"):
             path = env_path if (env_path == "launches" or persist_ok) else "launches"
         self.path = "persistent" if (path == "persistent" or (path == "auto" and persist_ok and PERSISTENT_BY_DEFAULT)) else "launches"
-        persistent = self.path == "persistent"
-        table = []
+
+    def _choose_attention(self, memory, fused: bool, kv32: bool) -> None:
+        """the form of the self and cross blocks: sets _attn_fused, kv32, _fuse_self, _fuse_cross, _chain"""
+        B, H, L = self.B, self.H, lib()
         # the attention block with the whole K stream in flight from the start (decode_persist.hip): opt-in, for A/B runs
-        v2 = os.environ.get("PM_DEC_ATTN_V2", "0") != "0" and max(S, self.Ttot) <= 2048 and hasattr(L, "pm_dec_attention_fused_v2")  # measured slower (527 vs 461 us per step): off
-        attn_fused = L.pm_dec_attention_fused_v2 if v2 else L.pm_dec_attention_fused
+        v2 = os.environ.get("PM_DEC_ATTN_V2", "0") != "0" and max(self.S, self.Ttot) <= 2048 and hasattr(L, "pm_dec_attention_fused_v2")  # measured slower (527 vs 461 us per step): off
+        self._attn_fused = L.pm_dec_attention_fused_v2 if v2 else L.pm_dec_attention_fused
         self.kv32 = bool(kv32)
-        kv_dt, kv_sz = (torch.float32, 4) if kv32 else (torch.bfloat16, 2)
         if kv32:
-            if persistent or not fused or B * H > 256 or os.environ.get("PM_DEC_FUSE_SELF") == "0" or os.environ.get("PM_DEC_FUSE_CROSS") == "0":
+            if self.path == "persistent" or not fused or B * H > 256 or os.environ.get("PM_DEC_FUSE_SELF") == "0" or os.environ.get("PM_DEC_FUSE_CROSS") == "0":
                 raise NotImplementedError("greedy decode: fp32 K/V caches run on the fused attention blocks (B * n_heads <= 256)")
-            attn_fused = L.pm_dec_attention_fused_kv32
-        self.B, self.P, self.n_steps = B, P, self.Ttot - 1
-        Tmax = self.Ttot
+            self._attn_fused = L.pm_dec_attention_fused_kv32
+        # the fused self block is one 512-thread workgroup per (sequence, head) that pulls the head's q/k/v weights
+        # (3 * 64 * d * 2 B) through its CU: it wins while every workgroup has a CU to itself (B * H <= 256 on MI355X:
+        # Whisper-base b = 32), beyond that the row-split projection + attention pair is faster (GPT-2 small b = 32,
+        # B * H = 384: 705 -> 641 us per step)
+        env_fs = os.environ.get("PM_DEC_FUSE_SELF")
+        self._fuse_self = fused and (B * H <= 256 if env_fs is None else env_fs != "0")
+        self._fuse_cross = fused and os.environ.get("PM_DEC_FUSE_CROSS", "1") != "0"
+        # the chain of deferred sums (pm_dec_attention_chain): the self block leaves its output projection as per-head partial
+        # sums that the cross block adds while it loads its row, fc2 leaves its K parts to the next layer's self block - one
+        # launch and one ticket pass per layer less.  Needs both blocks fused (their workgroups own whole rows).
+        self._chain = (self._fuse_self and self._fuse_cross and memory is not None and self.path != "persistent" and not v2
+                       and os.environ.get("PM_DEC_CHAIN", "1") != "0")
+
+    def _allocate(self, dec, memory, prompt: Tensor, margins: bool) -> None:
+        """the state of a run and the scratch rows of a step"""
+        B, d, V, E, L = self.B, self.d, self.V, self._E, lib()
+        dev = E.device
         f32 = dict(dtype=torch.float32, device=dev)
         self.x = torch.empty(B, d, **f32)
-        self.q = torch.empty(B, inner, **f32)
-        self.att = torch.empty(B, inner, **f32)
-        self.h = torch.empty(B, hid_max, **f32)  # widest MLP of the stack (mlp_ratio is free: transformer.py:77)
+        self.q = torch.empty(B, self.inner, **f32)
+        self.att = torch.empty(B, self.inner, **f32)
+        self.h = torch.empty(B, self._hid_max, **f32)  # widest MLP of the stack (mlp_ratio is free: transformer.py:77)
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.prompt = prompt.contiguous().to(dev)
         self.tok_cur = self.prompt[:, 0].clone()
         self.tokens = torch.zeros(B, self.Ttot, dtype=torch.int64, device=dev)
-        self.tokens[:, :P] = self.prompt
+        self.tokens[:, : self.P] = self.prompt
         self.margins = torch.zeros(B, self.Ttot, **f32) if margins else None
         # d_model > 512: the final LayerNorm runs once as its own launch and the vocabulary projection without the
         # in-kernel LayerNorm, whose register budget would halve the feature tile (GPT-2 small: 101 -> ~55 us per step)
         self.split_final_norm = (d // 32 + 3) // 4 > 4
         tile = 64 if self.split_final_norm else L.pm_dec_argmax_tile(d)
-        n_tiles = (V + tile - 1) // tile  # pm_dec_linear mode 2 leaves one (max, index) per tile and sequence
-        self.ws_val = torch.empty(B, n_tiles, **f32)
-        self.ws_idx = torch.empty(B, n_tiles, dtype=torch.int32, device=dev)
-        pos_f32 = _f32(dec, "pos", dec.pos_embs)
-        mem2 = memory.reshape(self.clips * S, d) if memory is not None else None
-        self._keep = [E, pos_f32, memory]  # tensors the launch list points into
-        self.launches = []  # (fn, args): raw pointers only -> the loop has no per-step Python work beyond ctypes
-
-        def add(fn, *args):
-            self.launches.append((fn, args))
-
-        # plain projections with a long K (fc2: K = 4 d) are split over workgroups along K: see pm_dec_linear_ksplit
-        ks_min = int(os.environ.get("PM_DEC_KSPLIT_MINK", "1024"))
-        self._ks_bufs, self._ks_cnts = [], []
-
-        def dec_linear_ks(x, K, w, bias, resid, out, N, act=0):
-            ksp = int(os.environ.get("PM_DEC_KSPLIT", "4"))
-            ksp = max(2, min(ksp, 8, K // 32))
-            nt, mt = (N + 15) // 16, (B + 15) // 16
-            mt = 1 if mt <= 1 else 2 if mt == 2 else 4  # row tiles of the kernel instantiation
-            ws = torch.empty(nt * ksp * mt * 256, **f32)
-            cnt = torch.zeros(nt * 4, dtype=torch.int32, device=dev)  # one ticket per (feature tile, row tile)
-            self._ks_bufs += [ws, cnt]
-            self._ks_cnts.append(cnt)
-            self._keep += [w, bias]
-            add(L.pm_dec_linear_ksplit, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _ptr(bias), _ptr(resid),
-                resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0), B, N, K, act, ksp,
-                ws.data_ptr(), cnt.data_ptr(), None)
-
-        def dec_linear(x, K, gamma, beta, eps, w, bias, resid, out, N, act=0, mode=0, kc=None, vc=None, ldo=None):
-            if mode == 0 and gamma is None and K >= ks_min and N <= 4096 and int(os.environ.get("PM_DEC_KSPLIT", "4")) > 1:
-                return dec_linear_ks(x, K, w, bias, resid, out, N, act)
-            self._keep += [w, bias, gamma, beta]
-            add(L.pm_dec_linear, x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), float(eps), w.data_ptr(), w.stride(0),
-                _ptr(bias), _ptr(resid), resid.stride(0) if resid is not None else 0, _ptr(out),
-                (out.stride(0) if out is not None else 0) if ldo is None else ldo, B, N, K, act, mode, _ptr(kc), _ptr(vc),
-                inner, H, Tmax, self.pos.data_ptr(), self.ws_val.data_ptr(), self.ws_idx.data_ptr(), None)
-
+        self._n_tiles = (V + tile - 1) // tile  # pm_dec_linear mode 2 leaves one (max, index) per tile and sequence
+        self.ws_val = torch.empty(B, self._n_tiles, **f32)
+        self.ws_idx = torch.empty(B, self._n_tiles, dtype=torch.int32, device=dev)
+        self._pos_tab = _f32(dec, "pos", dec.pos_embs)
+        self.keep(E, self._pos_tab, memory)
+        self._lin = dict(geom=(self.inner, self.H, self.Ttot), pos=self.pos, argmax_ws=(self.ws_val, self.ws_idx))
         # x for position 0 comes from reset(); every later x row is written by the previous step's pm_dec_next_token
-        self._embed0 = (L.pm_dec_embed, (self.tok_cur.data_ptr(), E.data_ptr(), pos_f32.data_ptr(), self.pos.data_ptr(),
+        self._embed0 = (L.pm_dec_embed, (self.tok_cur.data_ptr(), E.data_ptr(), self._pos_tab.data_ptr(), self.pos.data_ptr(),
                                          self.x.data_ptr(), B, d, V, None))
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.head_parts = self.x2 = self.fc2_parts = None
-        cur, oth, pending = self.x, None, None  # the residual stream's buffer; the other one; sums the next fused block must add
-        self.self_k, self.self_v, self.cross_kv, self._cross_w = [], [], [], []
-        for layer in dec.layers:
-            if not layer.pre_norm:
-                raise NotImplementedError("greedy decode: pre-norm layers only (the post-norm GPT decodes through forward())")
-            if (layer.ca is None) != (memory is None):
-                raise ValueError("greedy decode: cross-attention layers need a memory, decoder-only layers must not get one")
-            sa, ca, mlp = layer.sa, layer.ca, layer.mlp
-            kc = torch.empty(B, H, Tmax, 64, dtype=kv_dt, device=dev)
-            vc = torch.empty_like(kc)
-            self.self_k.append(kc)
-            self.self_v.append(vc)
-            wqkv, bqkv = sa._pack("qkv")
-            g, b = _f32(layer.sa_norm, "g", layer.sa_norm.weight), _f32(layer.sa_norm, "b", layer.sa_norm.bias)
-            self._keep += [wqkv, bqkv, g, b]
-            # the fused self block is one 512-thread workgroup per (sequence, head) that pulls the head's q/k/v weights
-            # (3 * 64 * d * 2 B) through its CU: it wins while every workgroup has a CU to itself (B * H <= 256 on MI355X:
-            # Whisper-base b = 32), beyond that the row-split projection + attention pair is faster (GPT-2 small b = 32,
-            # B * H = 384: 705 -> 641 us per step)
-            env_fs = os.environ.get("PM_DEC_FUSE_SELF")
-            fuse_self = fused and (B * H <= 256 if env_fs is None else env_fs != "0")
-            fuse_cross = fused and os.environ.get("PM_DEC_FUSE_CROSS", "1") != "0"
-            # the chain of deferred sums (pm_dec_attention_chain): the self block leaves its output projection as per-head partial
-            # sums that the cross block adds while it loads its row, fc2 leaves its K parts to the next layer's self block - one
-            # launch and one ticket pass per layer less.  Needs both blocks fused (their workgroups own whole rows).
-            chain = (fuse_self and fuse_cross and ca is not None and not persistent and not v2
-                     and os.environ.get("PM_DEC_CHAIN", "1") != "0")
-            if chain and self.head_parts is None:
-                self.head_parts = torch.empty(B * H * d, **f32)
-                self.x2 = torch.empty(B, d, **f32)
-                oth = self.x2
-            if persistent:
-                bo = _f32(sa.out_proj, "b", sa.out_proj.bias)
-                self._keep += [sa.out_proj.weight, bo]
-                ent = DecLayer(sa_g=g.data_ptr(), sa_b=b.data_ptr(), w_qkv=wqkv.data_ptr(), b_qkv=_ptr(bqkv), kc=kc.data_ptr(),
-                               vc=vc.data_ptr(), w_so=sa.out_proj.weight.data_ptr(), b_so=_ptr(bo), sa_eps=float(layer.sa_norm.eps))
-                table.append(ent)
-            elif chain:
-                bo = _f32(sa.out_proj, "b", sa.out_proj.bias)
-                self._keep += [sa.out_proj.weight, bo]
-                n_in, p_in, ps_in, pr_in, pb_in = pending or (0, None, 0, 0, None)
-                add(L.pm_dec_attention_chain, cur.data_ptr(), d, g.data_ptr(), b.data_ptr(), float(layer.sa_norm.eps),
-                    wqkv.data_ptr(), _ptr(bqkv), kc.data_ptr(), vc.data_ptr(), H * Tmax * 64, Tmax * 64, 64, self.pos.data_ptr(),
-                    0, Tmax, B, H, 1, int(kv32), p_in, n_in, ps_in, pr_in, pb_in, oth.data_ptr() if n_in else None,
-                    sa.out_proj.weight.data_ptr(), self.head_parts.data_ptr(), None, None)
-                if n_in:
-                    cur, oth = oth, cur
-                pending = (H, self.head_parts.data_ptr(), d, H * d, _ptr(bo))
-            elif fuse_self:  # LN + q/k/v projection + cache append + attention in one launch per layer
-                add(attn_fused, cur.data_ptr(), d, g.data_ptr(), b.data_ptr(), float(layer.sa_norm.eps),
-                    wqkv.data_ptr(), _ptr(bqkv), kc.data_ptr(), vc.data_ptr(), H * Tmax * 64, Tmax * 64, 64, self.pos.data_ptr(),
-                    0, Tmax, self.att.data_ptr(), B, H, 1, None)
-            else:
-                dec_linear(cur, d, g, b, layer.sa_norm.eps, wqkv, bqkv, None, self.q, 3 * inner, mode=1, kc=kc, vc=vc)
-                add(L.pm_dec_attention, self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), H * Tmax * 64, Tmax * 64, 64,
-                    self.pos.data_ptr(), 1, Tmax, self.att.data_ptr(), B, H, None)
-            if not persistent and not chain:
-                dec_linear(self.att, inner, None, None, 0.0, sa.out_proj.weight, _f32(sa.out_proj, "b", sa.out_proj.bias), cur,
-                           cur, d)
-            if ca is not None:
-                # cross attention: K/V of the memory projected ONCE (the reference re-projects them on every call,
-                # transformer.py:44-49), kept packed (B, S, [k | v]) in bf16
-                wkv, bkv = ca._pack("kv")
-                kv = self._project_memory(mem2, wkv, bkv)
-                self.cross_kv.append(kv)
-                self._cross_w.append((wkv, bkv))
-                g, b = _f32(layer.ca_norm, "g", layer.ca_norm.weight), _f32(layer.ca_norm, "b", layer.ca_norm.bias)
-                bq = _f32(ca.q_proj, "b", ca.q_proj.bias)
-                self._keep += [g, b, bq]
-                if persistent:
-                    bo = _f32(ca.out_proj, "b", ca.out_proj.bias)
-                    self._keep += [ca.q_proj.weight, ca.out_proj.weight, bo]
-                    ent.ca_g, ent.ca_b, ent.ca_eps = g.data_ptr(), b.data_ptr(), float(layer.ca_norm.eps)
-                    ent.w_q, ent.b_q, ent.cross_kv = ca.q_proj.weight.data_ptr(), _ptr(bq), kv.data_ptr()
-                    ent.w_co, ent.b_co = ca.out_proj.weight.data_ptr(), _ptr(bo)
-                elif chain:  # x = the stream + the self block's projection (heads in order) + its bias, formed while loading
-                    n_in, p_in, ps_in, pr_in, pb_in = pending
-                    add(L.pm_dec_attention_chain, cur.data_ptr(), d, g.data_ptr(), b.data_ptr(), float(layer.ca_norm.eps),
-                        ca.q_proj.weight.data_ptr(), _ptr(bq), kv.data_ptr(), kv.data_ptr() + inner * kv_sz, S * 2 * inner, 64,
-                        2 * inner, None, S, S, B, H, 0, int(kv32), p_in, n_in, ps_in, pr_in, pb_in, oth.data_ptr(), None, None,
-                        self.att.data_ptr(), None)
-                    cur, oth = oth, cur
-                    pending = None
-                elif fuse_cross:
-                    add(attn_fused, cur.data_ptr(), d, g.data_ptr(), b.data_ptr(), float(layer.ca_norm.eps),
-                        ca.q_proj.weight.data_ptr(), _ptr(bq), kv.data_ptr(), kv.data_ptr() + inner * kv_sz, S * 2 * inner, 64,
-                        2 * inner, None, S, S, self.att.data_ptr(), B, H, 0, None)
-                else:
-                    dec_linear(cur, d, g, b, layer.ca_norm.eps, ca.q_proj.weight, bq, None, self.q, inner)
-                    add(L.pm_dec_attention, self.q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 2, S * 2 * inner, 64,
-                        2 * inner, None, S, S, self.att.data_ptr(), B, H, None)
-                if not persistent:
-                    dec_linear(self.att, inner, None, None, 0.0, ca.out_proj.weight, _f32(ca.out_proj, "b", ca.out_proj.bias), cur,
-                               cur, d)
-            g, b = _f32(layer.mlp_norm, "g", layer.mlp_norm.weight), _f32(layer.mlp_norm, "b", layer.mlp_norm.bias)
-            if mlp.act_name not in ("gelu", "approximate_gelu"):
-                raise NotImplementedError("greedy decode: GELU / tanh-GELU MLPs only")
-            act_code = ops.ACT[mlp.act_name]
-            hid = mlp.linear1.out_features
-            if hid % 32 or mlp.linear2.in_features != hid or self.h[:, :hid].shape[1] != hid:
-                raise NotImplementedError(f"greedy decode: MLP hidden width {hid} must be a multiple of 32 and fit the scratch row")
-            if persistent:
-                b1, b2 = _f32(mlp.linear1, "b", mlp.linear1.bias), _f32(mlp.linear2, "b", mlp.linear2.bias)
-                self._keep += [g, b, mlp.linear1.weight, mlp.linear2.weight, b1, b2]
-                ent.mlp_g, ent.mlp_b, ent.mlp_eps = g.data_ptr(), b.data_ptr(), float(layer.mlp_norm.eps)
-                ent.w1, ent.b1, ent.w2, ent.b2 = mlp.linear1.weight.data_ptr(), _ptr(b1), mlp.linear2.weight.data_ptr(), _ptr(b2)
-                continue
-            dec_linear(cur, d, g, b, layer.mlp_norm.eps, mlp.linear1.weight, _f32(mlp.linear1, "b", mlp.linear1.bias), None,
-                       self.h[:, :hid], hid, act=act_code)
-            ksp = max(2, min(int(os.environ.get("PM_DEC_KSPLIT", "4")), 8, hid // 32))
-            if chain and layer is not dec.layers[-1] and hid >= ks_min and int(os.environ.get("PM_DEC_KSPLIT", "4")) > 1:
-                # fc2's K parts stay parts: the next layer's self block adds them (with the bias and this stream) while it loads
-                if self.fc2_parts is None:
-                    self.fc2_parts = torch.empty(8, B, d, **f32)
-                b2 = _f32(mlp.linear2, "b", mlp.linear2.bias)
-                self._keep += [mlp.linear2.weight, b2]
-                add(L.pm_dec_linear_kparts, self.h.data_ptr(), self.h.stride(0), mlp.linear2.weight.data_ptr(),
-                    mlp.linear2.weight.stride(0), self.fc2_parts.data_ptr(), d, B * d, B, d, hid, ksp, None)
-                pending = (ksp, self.fc2_parts.data_ptr(), B * d, d, _ptr(b2))
-            else:
-                dec_linear(self.h[:, :hid], hid, None, None, 0.0, mlp.linear2.weight, _f32(mlp.linear2, "b", mlp.linear2.bias),
-                           cur, cur, d)
-        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        if persistent:
-            import ctypes
+        self.fc2_parts = None
+        self.head_parts = torch.empty(B * self.H * d, **f32) if self._chain else None
+        self.x2 = torch.empty(B, d, **f32) if self._chain else None
+        # the chain's hand-off: the residual stream's buffer, the other one, the sums the next chain block must add
+        self._cur, self._oth, self._pending = self.x, self.x2, None
+        self.self_k, self.self_v, self.cross_kv, self._cross_w, self._table = [], [], [], [], []
 
-            arr = (DecLayer * len(table))(*table)
-            self.table = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8).to(dev)
-            mt = (B + 15) // 16
-            self.ps_cnt = torch.zeros(len(table) * 24, dtype=torch.int32, device=dev)
-            ws = torch.empty((d // 16) * mt * ksp_p * 256, **f32)
-            tick = torch.zeros((d // 16) * mt, dtype=torch.int32, device=dev)
-            self._ks_bufs += [ws, tick]
-            self._ks_cnts.append(tick)
-            add(L.pm_dec_layers, self.table.data_ptr(), len(table), B, d, H, S, Tmax, hid_max, ops.ACT[acts.pop()], ksp_p,
-                self.pos.data_ptr(), self.x.data_ptr(), self.att.data_ptr(), self.h.data_ptr(), self.h.stride(0),
-                self.ps_cnt.data_ptr(), ws.data_ptr(), tick.data_ptr(), self.err.data_ptr(), None)
-        g, b = _f32(dec.norm, "g", dec.norm.weight), _f32(dec.norm, "b", dec.norm.bias)
-        if not 1 <= topk <= 64:
-            raise ValueError("greedy decode: topk must be in 1..64")
-        self.topk = topk
-        xl, gl, bl = cur, g, b  # (the chain leaves the stream in x or x2; the next step's row always goes to x)
-        if self.split_final_norm:
-            self.xn = torch.empty(B, d, **f32)
-            self._keep += [g, b]
-            add(L.pm_layernorm, cur.data_ptr(), d, 1, g.data_ptr(), b.data_ptr(), float(dec.norm.eps), self.xn.data_ptr(), d, 1,
-                B, d, None)
-            xl, gl, bl = self.xn, None, None
-        if topk == 1 and rules is None and not self._beam:
-            dec_linear(xl, d, gl, bl, dec.norm.eps, E, None, None, None, V, mode=2, ldo=0)
+    # ---- the blocks of a layer
+    def _self_block(self, layer) -> None:
+        B, H, d, Tmax, L, sa, cur = self.B, self.H, self.d, self.Ttot, lib(), layer.sa, self._cur
+        kc = torch.empty(B, H, Tmax, 64, dtype=torch.float32 if self.kv32 else torch.bfloat16, device=cur.device)
+        vc = torch.empty_like(kc)
+        self.self_k.append(kc)
+        self.self_v.append(vc)
+        wqkv, bqkv = sa._pack("qkv")
+        ln = _ln(layer.sa_norm)
+        wo, bo = sa.out_proj.weight, _f32(sa.out_proj, "b", sa.out_proj.bias)
+        self.keep(wqkv, bqkv, ln[0], ln[1], wo, bo)
+        kv = plan.cache_kv(kc, vc)
+        if self.path == "persistent":
+            self._table.append(DecLayer())
+            self._record(sa_g=ln[0], sa_b=ln[1], w_qkv=wqkv, b_qkv=bqkv, kc=kc, vc=vc, w_so=wo, b_so=bo, sa_eps=float(ln[2]))
+        elif self._chain:
+            parts = self._pending
+            self.add(L.pm_dec_attention_chain, *plan.chain_args(
+                cur, ln, wqkv, bqkv, kv, B, H, self_attn=True, pos=self.pos, n_keys=Tmax, kv_f32=self.kv32, parts=parts,
+                x_out=self._oth if parts is not None else None, w_out=wo, head_parts=self.head_parts))
+            if parts is not None:
+                self._cur, self._oth = self._oth, self._cur
+            self._pending = plan.Parts(H, self.head_parts, d, H * d, bo)
+        elif self._fuse_self:  # LN + q/k/v projection + cache append + attention in one launch per layer
+            self.add(self._attn_fused, *plan.fused_args(cur, ln, wqkv, bqkv, kv, self.att, B, H, self_attn=True, pos=self.pos,
+                                                        n_keys=Tmax))
+        else:
+            self.linear(cur, wqkv, self.q, ln=ln, bias=bqkv, mode=1, cache=(kc, vc))
+            self.add(L.pm_dec_attention, *plan.attention_args(self.q, kv, self.att, B, H, pos=self.pos, lk_add=1, lk_max=Tmax))
+        if self.path != "persistent" and not self._chain:
+            self.linear(self.att, wo, cur, bias=bo, resid=cur)
+
+    def _cross_block(self, layer, mem2: Tensor) -> None:
+        """cross attention: K/V of the memory projected ONCE (the reference re-projects them on every call,
+        transformer.py:44-49), kept packed (B, S, [k | v]) in bf16"""
+        B, H, S, L, ca, cur = self.B, self.H, self.S, lib(), layer.ca, self._cur
+        wkv, bkv = ca._pack("kv")
+        kvt = self._project_memory(mem2, wkv, bkv)
+        self.cross_kv.append(kvt)
+        self._cross_w.append((wkv, bkv))
+        ln = _ln(layer.ca_norm)
+        wq, bq = ca.q_proj.weight, _f32(ca.q_proj, "b", ca.q_proj.bias)
+        wo, bo = ca.out_proj.weight, _f32(ca.out_proj, "b", ca.out_proj.bias)
+        self.keep(ln[0], ln[1], wq, bq)
+        kv = plan.packed_kv(kvt, S, self.inner)
+        if self.path == "persistent":
+            return self._record(ca_g=ln[0], ca_b=ln[1], ca_eps=float(ln[2]), w_q=wq, b_q=bq, cross_kv=kvt, w_co=wo, b_co=bo)
+        if self._chain:  # x = the stream + the self block's projection (heads in order) + its bias, formed while loading
+            self.add(L.pm_dec_attention_chain, *plan.chain_args(cur, ln, wq, bq, kv, B, H, self_attn=False, n_keys=S, kv_f32=self.kv32,
+                                                                parts=self._pending, x_out=self._oth, out=self.att))
+            self._cur, self._oth = self._oth, self._cur
+            self._pending = None
+        elif self._fuse_cross:
+            self.add(self._attn_fused, *plan.fused_args(cur, ln, wq, bq, kv, self.att, B, H, self_attn=False, n_keys=S))
+        else:
+            self.linear(cur, wq, self.q, ln=ln, bias=bq)
+            self.add(L.pm_dec_attention, *plan.attention_args(self.q, kv, self.att, B, H, pos=None, lk_add=S, lk_max=S))
+        self.linear(self.att, wo, self._cur, bias=bo, resid=self._cur)
+
+    def _mlp_block(self, layer, last: bool) -> None:
+        B, d, mlp, cur = self.B, self.d, layer.mlp, self._cur
+        ln = _ln(layer.mlp_norm)
+        if mlp.act_name not in ("gelu", "approximate_gelu"):
+            raise NotImplementedError("greedy decode: GELU / tanh-GELU MLPs only")
+        hid = mlp.linear1.out_features
+        if hid % 32 or mlp.linear2.in_features != hid or self.h[:, :hid].shape[1] != hid:
+            raise NotImplementedError(f"greedy decode: MLP hidden width {hid} must be a multiple of 32 and fit the scratch row")
+        w1, b1 = mlp.linear1.weight, _f32(mlp.linear1, "b", mlp.linear1.bias)
+        w2, b2 = mlp.linear2.weight, _f32(mlp.linear2, "b", mlp.linear2.bias)
+        if self.path == "persistent":
+            return self._record(mlp_g=ln[0], mlp_b=ln[1], mlp_eps=float(ln[2]), w1=w1, b1=b1, w2=w2, b2=b2)
+        self.linear(cur, w1, self.h[:, :hid], ln=ln, bias=b1, act=ops.ACT[mlp.act_name])
+        ksp = self.ksplit(hid)
+        if self._chain and not last and ksp:
+            # fc2's K parts stay parts: the next layer's self block adds them (with the bias and this stream) while it loads
+            if self.fc2_parts is None:
+                self.fc2_parts = torch.empty(8, B, d, dtype=torch.float32, device=cur.device)
+            self.keep(w2, b2)
+            self.add(lib().pm_dec_linear_kparts, *plan.kparts_args(self.h, w2, self.fc2_parts, B, ksp))
+            self._pending = plan.Parts(ksp, self.fc2_parts, B * d, d, b2)
+        else:
+            self.linear(self.h[:, :hid], w2, cur, bias=b2, resid=cur)
+
+    def _record(self, **fields) -> None:
+        """fields of the current layer's record of the persistent table: tensors go in as pointers and are kept alive"""
+        for name, v in fields.items():
+            if isinstance(v, Tensor):
+                self.keep(v)
+                v = v.data_ptr()
+            setattr(self._table[-1], name, v)
+
+    def _persistent_table(self, dec) -> None:
+        """the layers' records on the device and the one launch that walks them"""
+        import ctypes
+
+        B, d, table, dev = self.B, self.d, self._table, self._E.device
+        arr = (DecLayer * len(table))(*table)
+        self.table = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8).to(dev)
+        mt = (B + 15) // 16
+        self.ps_cnt = torch.zeros(len(table) * 24, dtype=torch.int32, device=dev)
+        ws = torch.empty((d // 16) * mt * self._ksp_p * 256, dtype=torch.float32, device=dev)
+        tick = torch.zeros((d // 16) * mt, dtype=torch.int32, device=dev)
+        self.keep(ws)
+        self._ks_cnts.append(tick)
+        self.add(lib().pm_dec_layers, self.table.data_ptr(), len(table), B, d, self.H, self.S, self.Ttot, self._hid_max,
+                 ops.ACT[dec.layers[0].mlp.act_name], self._ksp_p, self.pos.data_ptr(), self.x.data_ptr(), self.att.data_ptr(),
+                 self.h.data_ptr(), self.h.stride(0), self.ps_cnt.data_ptr(), ws.data_ptr(), tick.data_ptr(), self.err.data_ptr(), None)
+
+    # ---- from the last layer's row to the next token
+    def _final_norm(self, dec) -> tuple:
+        """(x, ln) for the vocabulary projection: the stream and the final LayerNorm, or (d_model > 512) the stream normed by a
+        launch of its own and no LayerNorm.  (The chain leaves the stream in x or x2; the next step's row always goes to x.)"""
+        g, b, eps = _ln(dec.norm)
+        if not self.split_final_norm:
+            return self._cur, (g, b, eps)
+        self.xn = torch.empty_like(self.x)
+        self.keep(g, b)
+        self.add(lib().pm_layernorm, self._cur.data_ptr(), self.d, 1, g.data_ptr(), b.data_ptr(), float(eps), self.xn.data_ptr(), self.d, 1,
+                 self.B, self.d, None)
+        return self.xn, (None, None, eps)
+
+    def _full_logits(self, xl: Tensor, ln: tuple, rules: "WhisperRules | None") -> None:
+        """logits of the last position for every row, then the logit filters (k = 1 after them = arg-max)"""
+        B, V, P, L = self.B, self.V, self.P, lib()
+        self.logits = torch.empty(B, V, dtype=torch.float32, device=xl.device)
+        self.linear(xl, self._E, self.logits, ln=ln, mode=0)
+        if rules is not None:
+            i32 = dict(dtype=torch.int32, device=xl.device)
+            sup, blk = torch.tensor(list(rules.suppress), **i32), torch.tensor(list(rules.blank), **i32)
+            if not (0 <= rules.eot < rules.timestamp_begin < V) or any(not 0 <= int(i) < V for i in (*rules.suppress, *rules.blank)):
+                raise ValueError("WhisperRules: need 0 <= eot < timestamp_begin < vocab and listed ids inside the vocabulary")
+            self.keep(sup, blk)
+            self.add(L.pm_dec_whisper_rules, self.logits.data_ptr(), self.logits.stride(0), V, self.tokens.data_ptr(), self.Ttot,
+                     self.pos.data_ptr(), P, rules.eot, rules.no_timestamps, rules.timestamp_begin, rules.max_initial_timestamp,
+                     sup.data_ptr() if sup.numel() else None, sup.numel(), blk.data_ptr() if blk.numel() else None, blk.numel(),
+                     B, None)
+
+    def _token_tail(self, dec, topk: int, seed: int, rules, margins: bool, eos) -> None:
+        B, d, V, P, E, L = self.B, self.d, self.V, self.P, self._E, lib()
+        xl, ln = self._final_norm(dec)
+        if topk == 1 and rules is None:
+            self.linear(xl, E, None, ln=ln, mode=2)
             # token choice + the next step's embedding row + position advance: one launch
-            add(L.pm_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), n_tiles, self.pos.data_ptr(),
-                self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot, _ptr(self.margins),
-                E.data_ptr(), pos_f32.data_ptr(), self.x.data_ptr(), d, V, self.ticket.data_ptr(), B, None)
+            self.add(L.pm_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), self._n_tiles, self.pos.data_ptr(),
+                     self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot, plan.ptr(self.margins),
+                     E.data_ptr(), self._pos_tab.data_ptr(), self.x.data_ptr(), d, V, self.ticket.data_ptr(), B, None)
         else:  # top-k sampling on the device (text/generator.py:30-32): full logits of the last position, then the draw
             if margins:
                 raise ValueError("greedy decode: margins are an arg-max diagnostic (topk == 1)")
-            self.logits = torch.empty(B, V, **f32)
-            dec_linear(xl, d, gl, bl, dec.norm.eps, E, None, None, self.logits, V, mode=0)
-            if rules is not None:  # logit filters between the projection and the choice (k = 1 below = arg-max)
-                i32 = dict(dtype=torch.int32, device=dev)
-                sup, blk = torch.tensor(list(rules.suppress), **i32), torch.tensor(list(rules.blank), **i32)
-                if not (0 <= rules.eot < rules.timestamp_begin < V) or any(not 0 <= int(i) < V for i in (*rules.suppress, *rules.blank)):
-                    raise ValueError("WhisperRules: need 0 <= eot < timestamp_begin < vocab and listed ids inside the vocabulary")
-                self._keep += [sup, blk]
-                add(L.pm_dec_whisper_rules, self.logits.data_ptr(), self.logits.stride(0), V, self.tokens.data_ptr(), self.Ttot,
-                    self.pos.data_ptr(), P, rules.eot, rules.no_timestamps, rules.timestamp_begin, rules.max_initial_timestamp,
-                    sup.data_ptr() if sup.numel() else None, sup.numel(), blk.data_ptr() if blk.numel() else None, blk.numel(),
-                    B, None)
-            if self._beam:
-                return self._beam_tail(add, L, E, pos_f32, rules, eos, V, d, H, Tmax)
-            add(L.pm_dec_sample_topk, self.logits.data_ptr(), self.logits.stride(0), V, topk, int(seed) & (2**64 - 1),
-                self.pos.data_ptr(), self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot,
-                E.data_ptr(), pos_f32.data_ptr(), self.x.data_ptr(), d, self.ticket.data_ptr(), B, None)
+            self._full_logits(xl, ln, rules)
+            self.add(L.pm_dec_sample_topk, self.logits.data_ptr(), self.logits.stride(0), V, topk, int(seed) & (2**64 - 1),
+                     self.pos.data_ptr(), self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot,
+                     E.data_ptr(), self._pos_tab.data_ptr(), self.x.data_ptr(), d, self.ticket.data_ptr(), B, None)
 
     def _project_memory(self, mem2: Tensor, wkv: Tensor, bkv, out: Tensor | None = None) -> Tensor:
         """packed cross K/V of the memory rows: bf16 GEMM, or (kv32) the exact fp32 product of the fp32 memory with the
@@ -397,50 +388,20 @@ class GreedyDecoder:
         self.prompt.copy_(prompt if self.W == 1 else prompt.repeat_interleave(self.W, 0))
         self.tokens[:, : self.P] = self.prompt
 
-    def step(self, log: dict | None = None) -> None:
-        st = torch.cuda.current_stream().cuda_stream
-        for fn, args in self.launches:
-            if log is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            rc = fn(*args[:-1], st)
-            if log is not None:
-                e1.record()
-                log.setdefault(fn.__name__, []).append((e0, e1, args))
-            if rc:
-                check(rc, fn.__name__)
-
     def reset(self) -> None:
         self.pos.zero_()
         self.ticket.zero_()
         self.err.zero_()
         if self.path == "persistent":
             self.ps_cnt.zero_()  # arrival counters count up by epochs of the position: zero with it
-        for cnt in self._ks_cnts:  # the K-split tickets return to zero by themselves; this covers an aborted run
-            cnt.zero_()
         self.tok_cur.copy_(self.prompt[:, 0])
-        fn, args = self._embed0  # x[b] = emb[prompt[b, 0]] + pos[0]
-        check(fn(*args[:-1], torch.cuda.current_stream().cuda_stream), "pm_dec_embed")
+        self.start()  # x[b] = emb[prompt[b, 0]] + pos[0]
 
     def run(self, graph: bool = True) -> Tensor:
-        if not graph:
-            self.reset()
-            for _ in range(self.n_steps):
-                self.step()
-            return self.tokens
-        if getattr(self, "_graph", None) is None:
-            self.reset()
-            self.step()  # eager warm-up: loads every kernel before capture
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-            self._graph = g
-        self.reset()
+        one_step = self.begin(graph)
         for _ in range(self.n_steps):
-            self._graph.replay()
+            one_step()
         return self.tokens
-
 
     def check(self) -> None:
         """Raise if a hand-off inside the persistent step kernel gave up (one read-back: call it where the tokens are consumed)."""
@@ -456,14 +417,35 @@ class BeamDecoder(GreedyDecoder):
     and replayed like the greedy step; parents, scores and the K/V re-gather never leave the device (DESIGN.md "Beam search").
     State: ``scores`` (B, W) f32, ``finished`` / ``parents`` (B, W) int32 (of the last step), ``tokens`` (B * W, P + n) int64,
     ``logits`` (B * W, V) f32 of the last step (after the rules), ``self_k`` / ``self_v`` per layer (B * W, H, P + n, 64)."""
-    _beam = True
 
     def __init__(self, dec, memory: Tensor | None, prompt: Tensor, n_new: int, beams: int, *, eos: int | None = None,
                  rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False, fused: bool = True) -> None:
         super().__init__(dec, memory, prompt, n_new, False, fused, 1, 0, rules, path, kv32, beams=beams, eos=eos)
 
-    def _beam_tail(self, add, L, E, pos_f32, rules, eos, V, d, H, Tmax) -> None:
-        dev, B, W = E.device, self.clips, self.W
+    def _check_request(self, path: str, topk: int, margins: bool) -> str:
+        if not 1 <= self.W <= 8:
+            raise ValueError("beam decode: beams must be in 1..8")
+        if path == "persistent":
+            raise NotImplementedError("beam decode: the persistent layer kernel follows one hypothesis per sequence (path='launches')")
+        if topk != 1 or margins:
+            raise ValueError("beam decode: topk sampling and arg-max margins are greedy decode's")
+        return "launches"
+
+    def _rows(self, dec, prompt: Tensor, kv32: bool) -> Tensor:
+        """row b * W + w = beam w of clip b"""
+        if self.clips * self.W > 64:
+            raise NotImplementedError("beam decode: at most 64 rows (sequences x beams) per call (shard larger batches)")
+        if self.W > self.V:
+            raise ValueError("beam decode: more beams than vocabulary entries")
+        if kv32 and self.clips * self.W * dec.layers[0].sa.n_heads > 256:
+            raise NotImplementedError("beam decode: fp32 K/V caches run on the fused attention blocks (B * beams * n_heads <= 256)")
+        return prompt.repeat_interleave(self.W, 0)
+
+    def _token_tail(self, dec, topk: int, seed: int, rules, margins: bool, eos) -> None:
+        """full logits (+ rules), then the W best continuations per clip, their bookkeeping and the caches' re-gather"""
+        self._full_logits(*self._final_norm(dec), rules)
+        B, W, V, E, L = self.clips, self.W, self.V, self._E, lib()
+        dev = E.device
         if eos is None and rules is not None:
             eos = rules.eot
         if eos is not None and not 0 <= int(eos) < V:
@@ -477,15 +459,15 @@ class BeamDecoder(GreedyDecoder):
         # the layers' (K, V) cache pointers, read by the one reorder launch
         self._cache_table = torch.tensor([c.data_ptr() for kv in zip(self.self_k, self.self_v) for c in kv], dtype=torch.int64,
                                          device=dev)
-        add(L.pm_dec_beam_topw, self.logits.data_ptr(), self.logits.stride(0), V, W, self.scores.data_ptr(),
-            self.finished.data_ptr(), self.eos, self.pos.data_ptr(), self.P, self._cand_score.data_ptr(),
-            self._cand_tok.data_ptr(), B * W, None)
-        add(L.pm_dec_beam_select, self._cand_score.data_ptr(), self._cand_tok.data_ptr(), W, self.scores.data_ptr(),
-            self.finished.data_ptr(), self.parents.data_ptr(), self.eos, self.tokens.data_ptr(), self.Ttot, self.pos.data_ptr(),
-            self.prompt.data_ptr(), self.P, self.tok_cur.data_ptr(), E.data_ptr(), pos_f32.data_ptr(), self.x.data_ptr(), d, V,
-            self.ticket.data_ptr(), B, None)
-        add(L.pm_dec_beam_reorder, self._cache_table.data_ptr(), self._cache_table.numel(), self.parents.data_ptr(),
-            self.pos.data_ptr(), B, W, H, Tmax, int(self.kv32), None)
+        self.add(L.pm_dec_beam_topw, self.logits.data_ptr(), self.logits.stride(0), V, W, self.scores.data_ptr(),
+                 self.finished.data_ptr(), self.eos, self.pos.data_ptr(), self.P, self._cand_score.data_ptr(),
+                 self._cand_tok.data_ptr(), B * W, None)
+        self.add(L.pm_dec_beam_select, self._cand_score.data_ptr(), self._cand_tok.data_ptr(), W, self.scores.data_ptr(),
+                 self.finished.data_ptr(), self.parents.data_ptr(), self.eos, self.tokens.data_ptr(), self.Ttot, self.pos.data_ptr(),
+                 self.prompt.data_ptr(), self.P, self.tok_cur.data_ptr(), E.data_ptr(), self._pos_tab.data_ptr(), self.x.data_ptr(),
+                 self.d, V, self.ticket.data_ptr(), B, None)
+        self.add(L.pm_dec_beam_reorder, self._cache_table.data_ptr(), self._cache_table.numel(), self.parents.data_ptr(),
+                 self.pos.data_ptr(), B, W, self.H, self.Ttot, int(self.kv32), None)
 
     def _project_memory(self, mem2: Tensor, wkv: Tensor, bkv, out: Tensor | None = None) -> Tensor:
         """cross K/V projected ONCE per clip, then copied to the clip's W rows (the attention blocks read one K/V image per row;

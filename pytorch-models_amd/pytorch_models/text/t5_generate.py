@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from .._hip import PM_F32, check, lib, ops
+from .._hip import PM_F32, decode_plan as plan, lib, ops
 from ..transformer import _f32, _wb, derived, require_bf16_params
 
 MAX_BATCH, MAX_D, MAX_KEYS = 64, 1024, 2048
@@ -37,11 +37,7 @@ def _interleaved_wv(geglu) -> Tensor:
                    lambda: torch.stack([w.detach(), v.detach()], 1).reshape(2 * w.shape[0], w.shape[1]).to(torch.bfloat16).contiguous())
 
 
-def _ptr(t: Tensor | None):
-    return None if t is None else t.data_ptr()
-
-
-class T5DecodeState:
+class T5DecodeState(plan.CapturedStep):
     """State + launch list of the decode step for one (model, batch, source length, prompt length, new tokens) geometry."""
 
     def __init__(self, model, B: int, S: int, P: int, n_new: int, pad_id: int = 0, eos_id: int = 1, return_logits: bool = False) -> None:
@@ -97,32 +93,10 @@ class T5DecodeState:
         self.ws_idx = torch.empty(B, n_tiles, **i32)
         self.logits_step = torch.empty(B, V, **f32) if return_logits else None
         self.logits = torch.zeros(B, Ttot - 1, V, **f32) if return_logits else None
-        self._keep = [E, Wc]
-        self._ks_bufs, self._ks_cnts = [], []
-        self.launches = []  # (fn, args): raw pointers only, the loop has no per-step Python work beyond ctypes
-
-        def add(fn, *args):
-            self.launches.append((fn, args))
-
-        def dec_linear(x, K, w, resid, out, N, mode=0):
-            """bias-free x w^T (+ resid) through pm_dec_linear (mode 2: arg-max tiles), split along a long K as GreedyDecoder does"""
-            self._keep.append(w)
-            if mode == 0 and K >= 1024 and N <= 4096:
-                ksp = max(2, min(4, K // 32))
-                mt = (B + 15) // 16
-                mt = 1 if mt <= 1 else 2 if mt == 2 else 4
-                ws = torch.empty(((N + 15) // 16) * ksp * mt * 256, **f32)
-                cnt = torch.zeros(((N + 15) // 16) * 4, **i32)
-                self._ks_bufs += [ws, cnt]
-                self._ks_cnts.append(cnt)
-                add(L.pm_dec_linear_ksplit, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), None, _ptr(resid),
-                    resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0), B, N, K, 0, ksp, ws.data_ptr(),
-                    cnt.data_ptr(), None)
-                return
-            add(L.pm_dec_linear, x.data_ptr(), x.stride(0), None, None, 0.0, w.data_ptr(), w.stride(0), None, _ptr(resid),
-                resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0) if out is not None else 0, B, N, K, 0, mode,
-                None, None, inner, H, Tmax, self.pos.data_ptr(), self.ws_val.data_ptr(), self.ws_idx.data_ptr(), None)
-
+        # bias-free x w^T (+ resid) through pm_dec_linear (mode 2: arg-max tiles), split along a long K as GreedyDecoder does
+        super().__init__(B, dev, k_split=4, ksplit_min_k=1024)
+        self.keep(E, Wc)
+        self._lin = dict(geom=(inner, H, Tmax), pos=self.pos, argmax_ws=(self.ws_val, self.ws_idx))
         # one workgroup per (sequence, head) pulls the head's q/k/v rows through its CU: that wins while every workgroup has a CU
         # to itself (B * H <= 256); beyond, the projection that reads the weights once per 8 sequences + an attention launch
         self.fuse_self = B * H <= 256
@@ -136,16 +110,16 @@ class T5DecodeState:
             self.self_v.append(vc)
             wqkv, _ = sa._pack("qkv")
             g = _f32(layer.sa_norm, "g", layer.sa_norm.weight)
-            self._keep += [wqkv, g]
+            self.keep(wqkv, g)
             if self.fuse_self:
-                add(L.pm_t5_dec_self_fused, x.data_ptr(), d, g.data_ptr(), float(layer.sa_norm.eps), wqkv.data_ptr(), kc.data_ptr(),
-                    vc.data_ptr(), Tmax, self.pos.data_ptr(), self.lut.data_ptr(), self.att.data_ptr(), B, H, None)
+                self.add(L.pm_t5_dec_self_fused, x.data_ptr(), d, g.data_ptr(), float(layer.sa_norm.eps), wqkv.data_ptr(), kc.data_ptr(),
+                         vc.data_ptr(), Tmax, self.pos.data_ptr(), self.lut.data_ptr(), self.att.data_ptr(), B, H, None)
             else:
-                add(L.pm_t5_dec_rms_qkv, x.data_ptr(), d, g.data_ptr(), float(layer.sa_norm.eps), wqkv.data_ptr(), self.q.data_ptr(),
-                    kc.data_ptr(), vc.data_ptr(), Tmax, self.pos.data_ptr(), B, H, None)
-                add(L.pm_t5_dec_self_attention, self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), Tmax, self.pos.data_ptr(),
-                    self.lut.data_ptr(), self.att.data_ptr(), B, H, None)
-            dec_linear(self.att, inner, _wb(sa.out_proj, "w", sa.out_proj.weight), x, x, d)
+                self.add(L.pm_t5_dec_rms_qkv, x.data_ptr(), d, g.data_ptr(), float(layer.sa_norm.eps), wqkv.data_ptr(), self.q.data_ptr(),
+                         kc.data_ptr(), vc.data_ptr(), Tmax, self.pos.data_ptr(), B, H, None)
+                self.add(L.pm_t5_dec_self_attention, self.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), Tmax, self.pos.data_ptr(),
+                         self.lut.data_ptr(), self.att.data_ptr(), B, H, None)
+            self.linear(self.att, _wb(sa.out_proj, "w", sa.out_proj.weight), x, resid=x)
             # cross attention: K/V of the memory projected ONCE per call into packed bf16 (B, S, [k | v]) (bind())
             wkv, _ = ca._pack("kv")
             kv = torch.empty(B * S, 2 * inner, dtype=torch.bfloat16, device=dev)
@@ -153,31 +127,28 @@ class T5DecodeState:
             self._cross_w.append(wkv)
             g = _f32(layer.ca_norm, "g", layer.ca_norm.weight)
             wq = _wb(ca.q_proj, "w", ca.q_proj.weight)
-            self._keep += [g, wq]
-            add(L.pm_t5_dec_cross_fused, x.data_ptr(), d, g.data_ptr(), float(layer.ca_norm.eps), wq.data_ptr(), kv.data_ptr(), S,
-                self.src_len.data_ptr(), self.att.data_ptr(), B, H, None)
-            dec_linear(self.att, inner, _wb(ca.out_proj, "w", ca.out_proj.weight), x, x, d)
+            self.keep(g, wq)
+            self.add(L.pm_t5_dec_cross_fused, x.data_ptr(), d, g.data_ptr(), float(layer.ca_norm.eps), wq.data_ptr(), kv.data_ptr(), S,
+                     self.src_len.data_ptr(), self.att.data_ptr(), B, H, None)
+            self.linear(self.att, _wb(ca.out_proj, "w", ca.out_proj.weight), x, resid=x)
             F = wo.in_features
             g = _f32(layer.mlp_norm, "g", layer.mlp_norm.weight)
             wv = _interleaved_wv(geglu)
-            self._keep += [g, wv]
-            add(L.pm_t5_dec_geglu, x.data_ptr(), d, g.data_ptr(), float(layer.mlp_norm.eps), wv.data_ptr(), self.h.data_ptr(),
-                self.h.stride(0), B, F, None)
-            dec_linear(self.h[:, :F], F, _wb(wo, "w", wo.weight), x, x, d)
+            self.keep(g, wv)
+            self.add(L.pm_t5_dec_geglu, x.data_ptr(), d, g.data_ptr(), float(layer.mlp_norm.eps), wv.data_ptr(), self.h.data_ptr(),
+                     self.h.stride(0), B, F, None)
+            self.linear(self.h[:, :F], _wb(wo, "w", wo.weight), x, resid=x)
         g = _f32(dec.norm, "g", dec.norm.weight)
-        self._keep.append(g)
-        add(L.pm_rmsnorm, x.data_ptr(), d, PM_F32, g.data_ptr(), float(dec.norm.eps), self.xn.data_ptr(), d, PM_F32, B, d, None)
-        dec_linear(self.xn, d, Wc, None, None, V, mode=2)
+        self.keep(g)
+        self.add(L.pm_rmsnorm, x.data_ptr(), d, PM_F32, g.data_ptr(), float(dec.norm.eps), self.xn.data_ptr(), d, PM_F32, B, d, None)
+        self.linear(self.xn, Wc, None, mode=2)
         if return_logits:  # the full last-position logits as well (diagnostics / tests): the same products, stored
-            add(L.pm_dec_linear, self.xn.data_ptr(), d, None, None, 0.0, Wc.data_ptr(), Wc.stride(0), None, None, 0,
-                self.logits_step.data_ptr(), V, B, V, d, 0, 0, None, None, inner, H, Tmax, self.pos.data_ptr(),
-                self.ws_val.data_ptr(), self.ws_idx.data_ptr(), None)
-        add(L.pm_t5_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), n_tiles, self.pos.data_ptr(),
-            self.prompt.data_ptr(), P, self.tokens.data_ptr(), Ttot, self.pad_id, self.eos_id, self.finished.data_ptr(),
-            self.out_len.data_ptr(), E.data_ptr(), x.data_ptr(), d, V, self.ticket.data_ptr(), _ptr(self.logits_step),
-            _ptr(self.logits), B, None)
+            self.add(L.pm_dec_linear, *plan.linear_args(self.xn, Wc, self.logits_step, B, **self._lin))
+        self.add(L.pm_t5_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), n_tiles, self.pos.data_ptr(),
+                 self.prompt.data_ptr(), P, self.tokens.data_ptr(), Ttot, self.pad_id, self.eos_id, self.finished.data_ptr(),
+                 self.out_len.data_ptr(), E.data_ptr(), x.data_ptr(), d, V, self.ticket.data_ptr(), plan.ptr(self.logits_step),
+                 plan.ptr(self.logits), B, None)
         self._embed0 = (L.pm_t5_dec_embed, (self.prompt.data_ptr(), P, E.data_ptr(), x.data_ptr(), B, d, V, None))
-        self._graph = None
         self.encoder_bias_bytes = 0
 
     # ---- per call: encoder (with source padding), cross K/V, prompt
@@ -217,44 +188,23 @@ class T5DecodeState:
         else:
             self.prompt.copy_(prompt)
 
-    def step(self) -> None:
-        st = torch.cuda.current_stream().cuda_stream
-        for fn, args in self.launches:
-            rc = fn(*args[:-1], st)
-            if rc:
-                check(rc, fn.__name__)
-
     def reset(self) -> None:
         self.pos.zero_()
         self.ticket.zero_()
         self.finished.zero_()
-        for cnt in self._ks_cnts:  # the K-split tickets return to zero by themselves; this covers an aborted run
-            cnt.zero_()
         self.out_len.fill_(self.Ttot)
         self.tokens.fill_(self.pad_id)
         self.tokens[:, : self.P] = self.prompt
         if self.logits is not None:
             self.logits.zero_()
-        fn, args = self._embed0  # x[b] = emb[prompt[b, 0]]
-        check(fn(*args[:-1], torch.cuda.current_stream().cuda_stream), "pm_t5_dec_embed")
+        self.start()  # x[b] = emb[prompt[b, 0]]
 
     def run(self, graph: bool = True) -> None:
-        if graph and self._graph is None:
-            self.reset()
-            self.step()  # eager warm-up: loads every kernel before the capture
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-            self._graph = g
-        self.reset()
+        one_step = self.begin(graph)
         # rows that have all produced eos emit nothing but pad (already in ``tokens``): look every POLL_EVERY steps
         poll = self.eos_id >= 0 and self.logits is None
         for i in range(self.n_steps):
-            if graph:
-                self._graph.replay()
-            else:
-                self.step()
+            one_step()
             if poll and i % POLL_EVERY == POLL_EVERY - 1 and i + 1 < self.n_steps and bool(self.finished.all()):
                 break
 
