@@ -287,6 +287,21 @@ int pm_dec_argmax_tile(int64_t K);
 int pm_dec_attention(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h, int64_t stride_k,
                      const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max, float* out, int64_t B, int64_t H, void* stream);
 
+/* The prompt pass of the KV-cached decoders: causal attention of a chunk of C consecutive positions p0 .. p0 + C - 1 over the
+ * step's caches, with the chunk's keys and values appended (csrc/prefill.hip; head_dim 64).  qkv: bf16, row b*C + i =
+ * [q | k | v] of position p0 + i (3*H*64 wide, leading dimension ld_qkv); kc / vc: the bf16 caches, addressed as in
+ * pm_dec_attention; out: bf16 (B*C, H*64), heads merged.  For every b, h, i < C:
+ *   kc / vc[b,h,p0+i,:] = the row's k_h / v_h, bit for bit;
+ *   out[b,i,h,:] = softmax_{j <= p0+i}(q . K_j / 8) V_j, K_j / V_j = the caches as they were for j < p0, the chunk's rows after.
+ * The mask is aligned to absolute positions (pm_attention_bf16's is top-left aligned).  No cache byte outside [p0, p0 + C) is
+ * written, and no workgroup reads a cache row that the launch writes.  p0 is a host integer: this runs outside the captured
+ * step.  PM_EINVAL before any HIP call for: a null pointer, C < 1, p0 < 0, p0 + C > lk_max, lk_max > 4096, ld_qkv < 3*H*64,
+ * ld_out < H*64, stride_k < 64, B*H > 65535, ld_qkv / strides not multiples of 8, ld_out not of 4, qkv / kc / vc not
+ * 16-byte aligned, out not 8-byte aligned. */
+int pm_prefill_attention_bf16(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b, int64_t stride_h,
+                              int64_t stride_k, void* out, int64_t ld_out, int64_t B, int64_t H, int64_t C, int64_t p0,
+                              int64_t lk_max, void* stream);
+
 /* pm_dec_linear, plain mode without LayerNorm, with K split over k_split (2..8) workgroups per 16-feature tile: each
  * part reads 1 / k_split of x (at M = 32, K = 2048 every workgroup of the unsplit kernel pulls all 256 KB of x through
  * one CU's L2 path) and of its weight rows; the last part to finish - an agent-scope ticket, no spinning - adds the

@@ -93,6 +93,12 @@ def attention_args(q: Tensor, kv: KV, out: Tensor, rows: int, heads: int, *, pos
     return (q.data_ptr(), *kv, ptr(pos), lk_add, lk_max, out.data_ptr(), rows, heads, None)
 
 
+def prefill_attention_args(qkv: Tensor, kv: KV, out: Tensor, rows: int, heads: int, chunk: int, p0: int, lk_max: int) -> tuple:
+    """pm_prefill_attention_bf16: ``chunk`` positions from p0 of each of ``rows`` sequences, [q | k | v] rows in, caches appended"""
+    return (qkv.data_ptr(), qkv.stride(0), kv.k, kv.v, kv.stride_b, kv.stride_h, kv.stride_k, out.data_ptr(), out.stride(0), rows,
+            heads, chunk, p0, lk_max, None)
+
+
 def fused_args(x: Tensor, ln, w: Tensor, bias, kv: KV, out: Tensor, rows: int, heads: int, *, self_attn: bool, pos=None,
                n_keys: int) -> tuple:
     """pm_dec_attention_fused / _fused_kv32 / _fused_v2: LayerNorm + projection (+ cache append) + attention, self or cross"""

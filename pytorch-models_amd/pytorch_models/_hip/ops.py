@@ -233,10 +233,10 @@ def attention_f32(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = 
 
 
 def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, out_dtype: torch.dtype | None = None,
-              act: str = "none", resid: Tensor | None = None) -> Tensor:
+              act: str = "none", resid: Tensor | None = None, out: Tensor | None = None) -> Tensor:
     """Row-wise LayerNorm of x (M, d) (bf16 | f32) with f32 gamma / beta (both None = no affine), optionally followed by
-    GELU and a residual add (pm_layernorm_ex)."""
-    _cuda(x, gamma, beta, resid)
+    GELU and a residual add (pm_layernorm_ex).  ``out``: a (M, d) row-major tensor to write instead of a new one."""
+    _cuda(x, gamma, beta, resid, out)
     _need(x.dim() == 2 and x.stride(1) == 1, "layernorm: x must be (M, d), row-major")
     M, d = x.shape
     _need((gamma is None) == (beta is None), "layernorm: gamma and beta come together")
@@ -245,7 +245,9 @@ def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, 
               "layernorm: gamma / beta must be f32 (d)")
     if resid is not None:
         _need(resid.shape == x.shape and resid.stride(1) == 1, "layernorm: resid must be (M, d), row-major")
-    out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
+    _need(out.shape == (M, d) and out.stride(1) == 1, "layernorm: out must be (M, d), row-major")
     gp, bp = (gamma.data_ptr(), beta.data_ptr()) if gamma is not None else (None, None)
     nbytes = float(M * d * (x.element_size() + out.element_size() + (resid.element_size() if resid is not None else 0)))
     if act == "none" and resid is None and gamma is not None:
@@ -284,12 +286,14 @@ def geglu(h: Tensor) -> Tensor:
     return out
 
 
-def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = False, bias: Tensor | None = None) -> Tensor:
+def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = False, bias: Tensor | None = None,
+              out: Tensor | None = None) -> Tensor:
     """q (B, Lq, H*hd), k / v (B, Lk, H*hd) bf16 views with unit last stride (e.g. column slices of a packed
     QKV projection) -> (B, Lq, H*hd) bf16, heads already merged.  bias: optional additive f32 (b, h, Lq, Lk) with
     b in {1, B}, h in {1, H} (size-1 dims broadcast).  head_dim 64 runs on the MFMA kernel, other head dims
-    (% 4 == 0 up to 128, % 2 == 0 up to 64: MobileViT's 16 .. 60) on the generic one."""
-    _cuda(q, k, v, bias)
+    (% 4 == 0 up to 128, % 2 == 0 up to 64: MobileViT's 16 .. 60) on the generic one.  ``out``: a bf16 (B, Lq, H*hd) tensor with
+    unit last stride to write instead of a new one."""
+    _cuda(q, k, v, bias, out)
     _need(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention: operands must be (B, L, H*hd)")
     B, Lq, D = q.shape
     Lk = k.shape[1]
@@ -297,7 +301,9 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
     hd = D // n_heads
     for t in (q, k, v):
         _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention: bf16 operands with unit last stride")
-    out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
+    if out is None:
+        out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
+    _need(out.shape == (B, Lq, D) and out.dtype == torch.bfloat16 and out.stride(2) == 1, "attention: out must be bf16 (B, Lq, H*hd)")
     args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
             v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, int(causal))
     sb = sh = sq = 0
@@ -582,9 +588,11 @@ def whisper_stem1(x: Tensor, w1: Tensor, b1: Tensor) -> Tensor:
 EMBED_CHECK_IDS = True  # embed_tokens validates ids against the vocabulary (one read-back per eager call)
 
 
-def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
-    """tokens int64 (B, L) -> (B, L, d): emb[tokens] + pos[pos0 : pos0 + L] (pos None: no positional term)."""
-    _cuda(tokens, emb, pos)
+def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0, out_dtype: torch.dtype = torch.bfloat16,
+                 out: Tensor | None = None) -> Tensor:
+    """tokens int64 (B, L) -> (B, L, d): emb[tokens] + pos[pos0 : pos0 + L] (pos None: no positional term).  ``out`` (bf16 table
+    only): a contiguous (B, L, d) tensor to write instead of a new one."""
+    _cuda(tokens, emb, pos, out)
     _need(tokens.dim() == 2 and tokens.dtype == torch.int64, "embed_tokens: tokens must be int64 (B, L)")
     tokens = tokens.contiguous()
     B, L = tokens.shape
@@ -603,12 +611,15 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
         _need(pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d and pos.shape[0] >= pos0 + L,
               f"embed_tokens: need {pos0 + L} position rows, have {pos.shape[0]}")
     if emb.dtype == torch.float32:  # fp32 table -> fp32 rows
+        _need(out is None, "embed_tokens: out= goes with a bf16 table")
         out = torch.empty((B, L, d), dtype=torch.float32, device=emb.device)
         rc = lib().pm_embed_tokens_f32(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr() if pos is not None else None, out.data_ptr(),
                                        B, L, pos0, d, V, _stream())
         check(rc, f"pm_embed_tokens_f32(B={B}, L={L}, d={d})")
         return out
-    out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
+    if out is None:
+        out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
+    _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens: out must be contiguous (B, L, d)")
     rc = lib().pm_embed_tokens(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr() if pos is not None else None, out.data_ptr(), _dt(out), B, L, pos0, d, V,
                                _stream())
     check(rc, f"pm_embed_tokens(B={B}, L={L}, d={d})")
@@ -665,6 +676,30 @@ def dec_attention(q: Tensor, k: Tensor, v: Tensor, lk: int) -> Tensor:
     B, H, T, _ = k.shape
     out = torch.empty_like(q)
     plan.call(lib().pm_dec_attention, plan.attention_args(q, plan.cache_kv(k, v), out, B, H, pos=None, lk_add=lk, lk_max=T), _stream())
+    return out
+
+
+def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int, out: Tensor | None = None) -> Tensor:
+    """pm_prefill_attention_bf16: the chunk of positions p0 .. p0 + C - 1 of every sequence attends, causally on absolute
+    positions, over the caches' keys < p0 and its own rows, and appends its k / v to the caches.  qkv bf16 (B * C, 3 * H * 64)
+    rows [q | k | v] with unit last stride; kc, vc bf16 (B, H, T, 64) caches (p0 + C <= T <= 4096) -> bf16 (B * C, H * 64)."""
+    _cuda(qkv, kc, vc, out)
+    _need(kc.dim() == 4 and kc.shape[3] == 64 and kc.shape[1] == n_heads and vc.shape == kc.shape and vc.stride() == kc.stride()
+          and kc.stride(3) == 1, "prefill_attention: caches must be (B, H, T, 64) with one layout and unit last stride")
+    B, H, T, _ = kc.shape
+    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1 and B > 0 and qkv.shape[0] % B == 0 and qkv.shape[0] > 0,
+          "prefill_attention: qkv must be (B * C, 3 * H * 64) rows with unit last stride, C >= 1")
+    for t in (qkv, kc, vc):
+        _need(t.dtype == torch.bfloat16, "prefill_attention: bf16 operands (fp32 caches keep the token-by-token prompt)")
+    C = qkv.shape[0] // B
+    _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
+    if out is None:
+        out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention: out must be bf16 (B * C, H * 64)")
+    kv = plan.cache_kv(kc, vc)
+    rc = _launch("prefill_attention", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_bf16(
+        *plan.prefill_attention_args(qkv, kv, out, B, H, C, p0, T)[:-1], _stream()))
+    check(rc, f"pm_prefill_attention_bf16(B={B}, H={H}, C={C}, p0={p0})")
     return out
 
 

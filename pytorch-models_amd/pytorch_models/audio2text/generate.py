@@ -50,15 +50,19 @@ class GreedyDecoder(plan.CapturedStep):
 
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
                  topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
-                 beams: int = 1, eos: int | None = None) -> None:
+                 beams: int = 1, eos: int | None = None, prefill: bool = False, prefill_chunk: int | None = None) -> None:
         """``kv32``: the reference-accuracy form of the same step - fp32 memory in, cross and self K/V kept in fp32 (nothing is
         rounded when it is cached; pm_dec_attention_fused_kv32), everything else as in the throughput path, whose projections
         are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it.
         ``beams`` > 1 (through BeamDecoder): the same step at B * beams rows (row b * beams + w) in full-logit mode, ending in
-        the beam kernels instead of a token choice; ``beams`` = 1 builds exactly the launch list it always did."""
+        the beam kernels instead of a token choice; ``beams`` = 1 builds exactly the launch list it always did.
+        ``prefill``: prompt positions 0 .. P - 2 go through the layers as one batched pass per ``prefill_chunk`` positions
+        (default 512, PM_PREFILL_CHUNK) that fills the self-attention caches (prefill()); the step then starts at position
+        P - 1 and runs n_new times instead of P + n_new - 1.  The step itself, and everything after the caches, is unchanged."""
         if path not in ("auto", "launches", "persistent"):
             raise ValueError("greedy decode: path must be 'auto', 'launches' or 'persistent'")
         self.W = int(beams)
+        path = self._check_prefill(dec, prefill, prefill_chunk, path, kv32)
         path = self._check_request(path, topk, margins)
         prompt = self._check_geometry(dec, memory, prompt, n_new, kv32)
         self._choose_path(dec, path, fused)
@@ -83,8 +87,28 @@ class GreedyDecoder(plan.CapturedStep):
             raise ValueError("greedy decode: topk must be in 1..64")
         self.topk = topk
         self._token_tail(dec, topk, seed, rules, margins, eos)
+        self._prefill_setup(dec)
 
     # ---- what is asked for
+    def _check_prefill(self, dec, prefill: bool, chunk: int | None, path: str, kv32: bool) -> str:
+        """the refusals of the prompt pass, before anything touches a device: each names the form that does run"""
+        self._prefill = bool(prefill)
+        self._prefill_chunk = int(os.environ.get("PM_PREFILL_CHUNK", "512")) if chunk is None else int(chunk)
+        if not prefill:
+            return path
+        if self._prefill_chunk < 1:
+            raise ValueError("greedy decode: prefill_chunk must be >= 1")
+        if path == "persistent":
+            raise NotImplementedError("greedy decode: prefill=True does not run on path='persistent' (its arrival counters are epochs "
+                                      "of the position, counted from 0); use path='launches', or prefill=False")
+        if kv32:
+            raise NotImplementedError("greedy decode: prefill=True fills bf16 caches; the fp32-cache step (kv32=True / exact=True) "
+                                      "promises bit equality with the reference and keeps the token-by-token prompt: prefill=False")
+        if dec.token_embs.weight.dtype == torch.float32:
+            raise NotImplementedError("greedy decode: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 parameters "
+                                      "decode through greedy_exact, token by token: prefill=False")
+        return "launches"  # 'auto' never picks the persistent kernel under prefill
+
     def _check_request(self, path: str, topk: int, margins: bool) -> str:
         if self.W != 1:
             raise ValueError("greedy decode: beams > 1 is BeamDecoder's")
@@ -374,6 +398,88 @@ class GreedyDecoder(plan.CapturedStep):
         w32 = derived(self, ("kv32w", wkv.data_ptr()), (wkv,), lambda: wkv.float())
         return ops.linear_f32(mem2, w32, bkv, out=out)
 
+    # ---- the prompt pass
+    def _prefill_setup(self, dec) -> None:
+        """the chunks of positions 0 .. P - 2, the layers' operands and the scratch of the widest chunk - all allocated here, so
+        that rebind() and repeated run() allocate nothing"""
+        n_pre = self.P - 1
+        self._pre_chunks = []
+        if not self._prefill or n_pre == 0:  # a one-token prompt has nothing to prefill: the run is the plain one
+            return
+        if self.Ttot > 4096:
+            raise NotImplementedError("greedy decode: prefill=True covers caches of up to 4096 positions")
+        B, d, inner, dev = self.B, self.d, self.inner, self._E.device
+        C = min(self._prefill_chunk, n_pre)
+        self._pre_chunks = [(p0, min(C, n_pre - p0)) for p0 in range(0, n_pre, C)]
+        self.n_steps = self.Ttot - self.P  # the step starts at position P - 1
+        bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
+        n = B * C
+        self._pre_tok = torch.empty(n, dtype=torch.int64, device=dev)
+        self._pre_x = [torch.empty(n * d, **f32), torch.empty(n * d, **f32)]  # the f32 residual stream, in and out of a block
+        self._pre_xn = torch.empty(n * d, **bf)
+        self._pre_qkv = torch.empty(n * 3 * inner, **bf)
+        self._pre_att = torch.empty(n * inner, **bf)
+        self._pre_h = torch.empty(n * self._hid_max, **bf)
+        self._pre_layers = []
+        for layer in dec.layers:
+            sa, ca, mlp = layer.sa, layer.ca, layer.mlp
+            rec = dict(sa_ln=_ln(layer.sa_norm), wqkv=sa._pack("qkv"), so=(sa.out_proj.weight, _f32(sa.out_proj, "b", sa.out_proj.bias)))
+            if ca is not None:
+                rec.update(ca_ln=_ln(layer.ca_norm), wq=(ca.q_proj.weight, _f32(ca.q_proj, "b", ca.q_proj.bias)),
+                           co=(ca.out_proj.weight, _f32(ca.out_proj, "b", ca.out_proj.bias)))
+            rec.update(mlp_ln=_ln(layer.mlp_norm), w1=(mlp.linear1.weight, _f32(mlp.linear1, "b", mlp.linear1.bias)),
+                       w2=(mlp.linear2.weight, _f32(mlp.linear2, "b", mlp.linear2.bias)), act=mlp.act_name)
+            self._pre_layers.append(rec)
+
+    def _prefill_chunk_pass(self, p0: int, c: int, log: list | None) -> None:
+        """positions p0 .. p0 + c - 1 of every row through the layers: bf16 where forward() rounds (LayerNorm output, q/k/v,
+        attention output, MLP hidden), the residual stream in f32 like the step's.  The last layer stops after its attention
+        kernel: the caches are full then, and the step recomputes position P - 1 from its own embedding row."""
+        B, d, H, inner, S = self.B, self.d, self.H, self.inner, self.S
+        n = B * c
+        view = lambda buf, cols: buf[: n * cols].view(n, cols)  # noqa: E731
+        tok = self._pre_tok[:n].view(B, c)
+        tok.copy_(self.prompt[:, p0 : p0 + c])
+        x, y = view(self._pre_x[0], d), view(self._pre_x[1], d)
+        xn, qkv, att, q = view(self._pre_xn, d), view(self._pre_qkv, 3 * inner), view(self._pre_att, inner), view(self._pre_qkv, inner)
+        ops.embed_tokens(tok, self._E, self._pos_tab, pos0=p0, out_dtype=torch.float32, out=x.view(B, c, d))
+        for l, rec in enumerate(self._pre_layers):
+            if log is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                log.append((l, e0, e1))
+            ops.layernorm(x, *rec["sa_ln"], out=xn)
+            ops.linear(xn, *rec["wqkv"], out=qkv)
+            ops.prefill_attention(qkv, self.self_k[l], self.self_v[l], H, p0, out=att)
+            if l + 1 < len(self._pre_layers):
+                ops.linear(att, *rec["so"], resid=x, out=y)
+                x, y = y, x
+                if "wq" in rec:
+                    kv = self.cross_kv[l].view(B, S, 2 * inner)
+                    ops.layernorm(x, *rec["ca_ln"], out=xn)
+                    ops.linear(xn, *rec["wq"], out=q)
+                    ops.attention(q.view(B, c, inner), kv[..., :inner], kv[..., inner:], H, out=att.view(B, c, inner))
+                    ops.linear(att, *rec["co"], resid=x, out=y)
+                    x, y = y, x
+                hid = rec["w1"][0].shape[0]
+                h = view(self._pre_h, hid)
+                ops.layernorm(x, *rec["mlp_ln"], out=xn)
+                ops.linear(xn, *rec["w1"], act=rec["act"], out=h)
+                ops.linear(h, *rec["w2"], resid=x, out=y)
+                x, y = y, x
+            if log is not None:
+                e1.record()
+
+    def prefill(self, log: list | None = None) -> None:
+        """After reset(): fill every layer's self-attention caches for positions 0 .. P - 2, chunk by chunk (eagerly, outside
+        the captured step: a chunk's first position is a host integer), then put the step at position P - 1 with the last
+        prompt token.  ``log`` collects (layer, start event, end event) per layer and chunk."""
+        for p0, c in self._pre_chunks:
+            self._prefill_chunk_pass(p0, c, log)
+        self.pos.fill_(self.P - 1)
+        self.tok_cur.copy_(self.prompt[:, self.P - 1])
+        self.start()  # x[b] = emb[prompt[b, P - 1]] + pos[P - 1]
+
     def rebind(self, memory: Tensor, prompt: Tensor) -> None:
         """New clips, same geometry: re-project the cross K/V INTO the existing buffers and swap the prompt, so the
         captured graph (which holds raw pointers) stays valid."""
@@ -399,6 +505,8 @@ class GreedyDecoder(plan.CapturedStep):
 
     def run(self, graph: bool = True) -> Tensor:
         one_step = self.begin(graph)
+        if self._pre_chunks:
+            self.prefill()
         for _ in range(self.n_steps):
             one_step()
         return self.tokens
@@ -416,11 +524,15 @@ class BeamDecoder(GreedyDecoder):
     full-logit mode, then pm_dec_whisper_rules (optional), pm_dec_beam_topw, pm_dec_beam_select, pm_dec_beam_reorder - captured
     and replayed like the greedy step; parents, scores and the K/V re-gather never leave the device (DESIGN.md "Beam search").
     State: ``scores`` (B, W) f32, ``finished`` / ``parents`` (B, W) int32 (of the last step), ``tokens`` (B * W, P + n) int64,
-    ``logits`` (B * W, V) f32 of the last step (after the rules), ``self_k`` / ``self_v`` per layer (B * W, H, P + n, 64)."""
+    ``logits`` (B * W, V) f32 of the last step (after the rules), ``self_k`` / ``self_v`` per layer (B * W, H, P + n, 64).
+    ``prefill``: GreedyDecoder's prompt pass at all B * W rows - the W rows of a clip hold the same prompt, so their caches come
+    out identical up to position P - 2, which is what the beam kernels assume at the first generated position."""
 
     def __init__(self, dec, memory: Tensor | None, prompt: Tensor, n_new: int, beams: int, *, eos: int | None = None,
-                 rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False, fused: bool = True) -> None:
-        super().__init__(dec, memory, prompt, n_new, False, fused, 1, 0, rules, path, kv32, beams=beams, eos=eos)
+                 rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False, fused: bool = True,
+                 prefill: bool = False, prefill_chunk: int | None = None) -> None:
+        super().__init__(dec, memory, prompt, n_new, False, fused, 1, 0, rules, path, kv32, beams=beams, eos=eos, prefill=prefill,
+                         prefill_chunk=prefill_chunk)
 
     def _check_request(self, path: str, topk: int, margins: bool) -> str:
         if not 1 <= self.W <= 8:
@@ -495,12 +607,14 @@ class BeamDecoder(GreedyDecoder):
 @torch.no_grad()
 def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams: int, eos_token_id: int | None = None,
                 graph: bool = True, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
-                return_beams: bool = False):
+                return_beams: bool = False, prefill: bool = False, prefill_chunk: int | None = None):
     """Beam search of width ``beams`` (1..8, B * beams <= 64): the best hypothesis per sequence, (B, P + n_new) int64, or with
     ``return_beams`` (tokens (B, beams, P + n_new), scores (B, beams) f32 = sum of the tokens' log-probabilities), best first.
     No length penalty, no early exit: always n_new steps; a hypothesis that emitted ``eos_token_id`` (default: rules.eot when
-    rules are given, else none) is extended with it at no cost."""
-    st = BeamDecoder(dec, memory, prompt, n_new, beams, eos=eos_token_id, rules=rules, path=path, kv32=kv32)
+    rules are given, else none) is extended with it at no cost.  ``prefill`` / ``prefill_chunk``: as in greedy_decode, at the
+    B * beams rows."""
+    st = BeamDecoder(dec, memory, prompt, n_new, beams, eos=eos_token_id, rules=rules, path=path, kv32=kv32, prefill=prefill,
+                     prefill_chunk=prefill_chunk)
     st.run(graph)
     toks, scores = st.beams()
     return (toks.clone(), scores.clone()) if return_beams else toks[:, 0].clone()
@@ -509,12 +623,16 @@ def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams
 @torch.no_grad()
 def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: bool = True, margins: bool = False,
                   fused: bool = True, topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto",
-                  kv32: bool = False):
+                  kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None):
     """tokens (B, P + n_new) int64 [and per-position diagnostic margins].  fused=False uses the unfused
     projection + attention launches (same arithmetic, 2 more launches per layer); topk > 1 samples each token from the
     softmax over the k largest logits on the device (same seed -> same ids); path: "persistent" (all layers of a step in
-    one launch), "launches" (a launch per stage) or "auto"."""
-    st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32)
+    one launch), "launches" (a launch per stage) or "auto".  ``prefill``: the prompt's positions 0 .. P - 2 fill the caches in
+    one batched pass per ``prefill_chunk`` positions (default 512) instead of one decode step each, and the step runs n_new
+    times; bf16 parameters and caches, not path="persistent" (NotImplementedError otherwise).  The prompt pass rounds where
+    forward() does, so its ids follow forward()'s contract (rel-L2 2e-2 on the logits), not the step's fp32-exact projections."""
+    st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32, prefill=prefill,
+                       prefill_chunk=prefill_chunk)
     toks = st.run(graph)
     st.check()
     return (toks, st.margins) if margins else toks

@@ -117,25 +117,30 @@ class WhisperDecoder(nn.Module):
 
     @torch.no_grad()
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
-                 path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False):
+                 path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
+                 prefill: bool = False):
         """Batched greedy decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids.  ``rules``: a
         generate.WhisperRules (token suppression, timestamp pairing / monotonicity) applied to the logits on the device;
         ``path``: "persistent" / "launches" / "auto" (generate.GreedyDecoder).  ``beams`` > 1: beam search of that width
         (generate.beam_decode; 1..8, B * beams <= 64) - the best hypothesis, or with ``return_beams`` (tokens (B, beams, P + n),
-        scores (B, beams)), best first; ``eos_token_id`` ends a hypothesis (default: rules.eot under rules)."""
+        scores (B, beams)), best first; ``eos_token_id`` ends a hypothesis (default: rules.eot under rules).  ``prefill``: the
+        prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode; bf16 model and memory)."""
         from .generate import beam_decode, greedy_decode, greedy_exact
 
+        if prefill and self.token_embs.weight.dtype == torch.float32:
+            raise NotImplementedError("WhisperDecoder.generate: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 "
+                                      "parameters decode through greedy_exact, token by token: prefill=False")
         if beams != 1 or return_beams:
             if self.token_embs.weight.dtype == torch.float32:
                 raise NotImplementedError("beam decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda()); "
                                           "Whisper.generate(exact=True) is the fp32-cache form")
             return beam_decode(self, memory, prompt, max_new_tokens, beams=beams, eos_token_id=eos_token_id, graph=graph,
-                               rules=rules, path=path, kv32=memory.dtype == torch.float32, return_beams=return_beams)
+                               rules=rules, path=path, kv32=memory.dtype == torch.float32, return_beams=return_beams, prefill=prefill)
         if self.token_embs.weight.dtype == torch.float32:  # fp32 parameters: the fp32 end-to-end loop (no bf16 storage points)
             if rules is not None:
                 raise NotImplementedError("WhisperDecoder.generate: the decoding rules run on the bf16 model's step kernels")
             return greedy_exact(self, memory, prompt, max_new_tokens)
-        return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path)
+        return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill)
 
 
 class Whisper(nn.Module):
@@ -153,20 +158,24 @@ class Whisper(nn.Module):
 
     @torch.no_grad()
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",
-                 exact: bool = False, beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False):
+                 exact: bool = False, beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
+                 prefill: bool = False):
         """log-mel (B, n_mels, T) + prompt ids (B, P) -> greedy ids (B, P + max_new_tokens); ``beams`` > 1: beam search
         (WhisperDecoder.generate), with ``exact=True`` on the fp32-cache step (B * beams * n_heads <= 256).
         ``exact=True`` (bf16 model): the whole pipeline - encoder, cross K/V, decoder, caches - in fp32 on an fp32 copy of
         this model's (bf16-valued) weights: the ids are those of the reference's fp32 forward on the same weights, bit for
         bit (tests/test_hip_exact.py); costs ~10x the bf16 encoder and an eager fp32 step loop.  A model whose
-        parameters are fp32 always decodes this way."""
+        parameters are fp32 always decodes this way.  ``prefill``: WhisperDecoder.generate's; not with ``exact``."""
+        if prefill and exact:
+            raise NotImplementedError("Whisper.generate: prefill=True fills bf16 caches; exact=True promises bit equality with the "
+                                      "reference and keeps the token-by-token prompt: prefill=False")
         if beams != 1 or return_beams:
             w = self.decoder.token_embs.weight
             if w.dtype == torch.float32 or not w.is_cuda:
                 raise NotImplementedError("beam decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda())")
             memory = self.exact_copy().encoder(x) if exact else self.encoder(x)
             return self.decoder.generate(memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, beams=beams,
-                                         eos_token_id=eos_token_id, return_beams=return_beams)
+                                         eos_token_id=eos_token_id, return_beams=return_beams, prefill=prefill)
         if exact and self.decoder.token_embs.weight.dtype != torch.float32:
             # fp32 encoder on the fp32 twin of the (bf16-valued) weights; the decode step is the throughput path's own launch
             # list with fp32 K / V caches - its projections are fp32-exact as they stand (bf16 weights x activations in three
@@ -179,7 +188,7 @@ class Whisper(nn.Module):
             if rules is None and prompt.shape[0] * H <= 256 and prompt.shape[0] <= 64:
                 return greedy_decode(self.decoder, twin.encoder(x), prompt, max_new_tokens, graph=graph, kv32=True)
             return twin.generate(x, prompt, max_new_tokens)
-        return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path)
+        return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill)
 
     def exact_copy(self) -> "Whisper":
         """fp32 twin of this model (same values: bf16 -> fp32 is exact), rebuilt when a parameter changes."""

@@ -18,9 +18,10 @@ class DecoderGenerator:
 
     @torch.inference_mode()
     def generate_ids(self, tokens: list[int], max_tokens: int = 100, topk: int = 1, eos_token_id: int | None = None,
-                     generator: torch.Generator | None = None, seed: int = 0) -> list[int]:
+                     generator: torch.Generator | None = None, seed: int = 0, prefill: bool = False) -> list[int]:
         """Token-level form of generate(): prompt ids -> prompt + new ids, stopping after eos_token_id (kept, as the
-        reference keeps it) or max_tokens new tokens."""
+        reference keeps it) or max_tokens new tokens.  ``prefill``: passed to the model's KV-cached generate() (the prompt in
+        one batched pass); a model that decodes another way refuses it."""
         p0 = next(self.model.parameters())
         device = p0.device
         tokens = list(tokens)
@@ -32,11 +33,15 @@ class DecoderGenerator:
         # a model without a position table (anything that is not one of this package's decoders) has no length limit here
         room = self.model.pos_embs.shape[0] - n if hasattr(self.model, "pos_embs") else max_tokens
         if topk <= 64 and hasattr(self.model, "generate") and kv_ok:
-            out = self.model.generate(torch.tensor([tokens], device=device), min(max_tokens, room), topk=topk, seed=seed)[0].tolist()
+            out = self.model.generate(torch.tensor([tokens], device=device), min(max_tokens, room), topk=topk, seed=seed,
+                                      **({"prefill": True} if prefill else {}))[0].tolist()
             new = out[n:]
             if eos_token_id is not None and eos_token_id in new:
                 new = new[: new.index(eos_token_id) + 1]
             return tokens + new
+        if prefill:
+            raise NotImplementedError("DecoderGenerator: prefill=True runs on the KV-cached step kernels (a bf16 pre-norm model "
+                                      "with generate(): GPT-2); this model decodes token by token: prefill=False")
         if topk == 1 and hasattr(self.model, "token_embs") and hasattr(self.model, "pos_embs"):
             from ..audio2text.generate import greedy_exact
             from ..transformer import derived
@@ -69,6 +74,7 @@ class DecoderGenerator:
                 break
         return tokens
 
-    def generate(self, prompt: str, max_tokens: int = 100, topk: int = 1) -> str:
-        ids = self.generate_ids(self.tokenizer.encode(prompt), max_tokens, topk, getattr(self.tokenizer, "eos_token_id", None))
+    def generate(self, prompt: str, max_tokens: int = 100, topk: int = 1, prefill: bool = False) -> str:
+        ids = self.generate_ids(self.tokenizer.encode(prompt), max_tokens, topk, getattr(self.tokenizer, "eos_token_id", None),
+                                prefill=prefill)
         return self.tokenizer.decode(ids)

@@ -50,22 +50,27 @@ class GPT2(nn.Module):
 
     @torch.no_grad()
     def generate(self, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, topk: int = 1, seed: int = 0,
-                 path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False):
+                 path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
+                 prefill: bool = False):
         """Batched decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids; greedy (topk = 1) or
         top-k sampling on the device (softmax over the k largest logits; the same seed gives the same ids); ``beams`` > 1:
-        beam search (audio2text.generate.beam_decode), with ``return_beams`` (tokens (B, beams, P + n), scores (B, beams))."""
+        beam search (audio2text.generate.beam_decode), with ``return_beams`` (tokens (B, beams, P + n), scores (B, beams)).
+        ``prefill``: the prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode)."""
         from ..audio2text.generate import beam_decode, greedy_decode, greedy_exact
 
+        if prefill and self.token_embs.weight.dtype == torch.float32:
+            raise NotImplementedError("GPT2.generate: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 parameters "
+                                      "decode through greedy_exact, token by token: prefill=False")
         if beams != 1 or return_beams:
             if self.token_embs.weight.dtype == torch.float32:
                 raise NotImplementedError("beam decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda())")
             if topk != 1:
                 raise ValueError("beam decode: topk sampling and arg-max margins are greedy decode's")
             return beam_decode(self, None, prompt, max_new_tokens, beams=beams, eos_token_id=eos_token_id, graph=graph, path=path,
-                               return_beams=return_beams)
+                               return_beams=return_beams, prefill=prefill)
         if self.token_embs.weight.dtype == torch.float32 and topk == 1:  # fp32 parameters: fp32 end to end
             return greedy_exact(self, None, prompt, max_new_tokens)
-        return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path)
+        return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path, prefill=prefill)
 
     @staticmethod
     def from_hf(model_tag: str, *, pretrained=False, **kwargs) -> "GPT2":
