@@ -423,6 +423,42 @@ int pm_dec_beam_select(const float* cand_score, const int32_t* cand_tok, int64_t
 int pm_dec_beam_reorder(const void* table, int64_t n_caches, const int32_t* parents, const int32_t* pos_ptr, int64_t B, int64_t W,
                         int64_t H, int64_t Tmax, int kv_f32, void* stream);
 
+/* Ragged prompt batches: sequences of different prompt lengths decode in one batch by being RIGHT-ALIGNED in
+ * the caches.  With Pm the longest prompt, sequence b's tokens sit at cache positions key_start[b] = Pm - len_b .. Pm - 1 and all
+ * sequences generate at Pm, Pm + 1, ... together, so the step keeps its single *pos_ptr.  Cache position t of sequence b is its
+ * logical position t - key_start[b] (the positional row), and its attention never sees keys below key_start[b].  key_start: int32,
+ * one per sequence, in DEVICE memory (a captured step serves any lengths).  Each entry point is its plain namesake plus key_start
+ * (PM_EINVAL when it is null); key_start all zero gives the plain result bit for bit.
+ *
+ * pm_dec_attention_ragged: sequence b attends keys lo .. Lk - 1, lo = min(key_start[b], Lk - 1) - pm_dec_attention on the caches
+ * advanced by lo keys, bit for bit; a start at or past Lk (a row still inside its padding) leaves the newest key. */
+int pm_dec_attention_ragged(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h, int64_t stride_k,
+                            const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max, const int32_t* key_start, float* out, int64_t B,
+                            int64_t H, void* stream);
+/* pm_prefill_attention_ragged_bf16: the query at position p = p0 + i of sequence b keeps keys lo(p) <= j <= p with
+ * lo(p) = min(key_start[b], p); a padded query (p < key_start[b]) sees itself only (its output is its own v row).  The append is
+ * pm_prefill_attention_bf16's: all C rows of the chunk are bit-copied, no byte outside [p0, p0 + C) is written. */
+int pm_prefill_attention_ragged_bf16(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b, int64_t stride_h,
+                                     int64_t stride_k, void* out, int64_t ld_out, int64_t B, int64_t H, int64_t C, int64_t p0,
+                                     int64_t lk_max, const int32_t* key_start, void* stream);
+/* out[b, l, :] = emb[tokens[b, l], :] + pos[max(0, pos0 + l - key_start[b]), :] (pos is required) */
+int pm_embed_tokens_ragged(const int64_t* tokens, const void* emb, const float* pos, const int32_t* key_start, void* out,
+                           int out_dtype, int64_t B, int64_t L, int64_t pos0, int64_t d, int64_t V, void* stream);
+/* x[b, :] = emb[tok_cur[b], :] + pos[max(0, t - key_start[b]), :] */
+int pm_dec_embed_ragged(const int64_t* tok_cur, const void* emb, const float* pos, const int32_t* pos_ptr,
+                        const int32_t* key_start, float* x, int64_t B, int64_t d, int64_t V, void* stream);
+/* pm_dec_next_token / pm_dec_sample_topk whose next row is x[b] = emb[token] + pos[max(0, t + 1 - key_start[b])]; prompt is the
+ * right-aligned (B, P) matrix; token choice, prompt forcing, margins, the draw (keyed by the CACHE position) and the ticketed
+ * advance are the plain kernels'. */
+int pm_dec_next_token_ragged(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr, const int64_t* prompt,
+                             int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot, float* margin_out, const void* emb,
+                             const float* pos, const int32_t* key_start, float* x, int64_t d, int64_t V, int32_t* ticket,
+                             int64_t B, void* stream);
+int pm_dec_sample_topk_ragged(const float* logits, int64_t ldl, int64_t V, int64_t k, uint64_t seed, int32_t* pos_ptr,
+                              const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                              const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d, int32_t* ticket,
+                              int64_t B, void* stream);
+
 /* ConvNeXt (reference: pytorch_models/image/convnext.py), csrc/convnext.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype
  * PM_BF16 or PM_F32; gamma / beta / bias f32.  The pointwise MLP and the downsample's Conv2d(C, 2C, 2, 2) run on the GEMMs above.
  *

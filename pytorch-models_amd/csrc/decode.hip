@@ -808,13 +808,23 @@ __global__ __launch_bounds__(64 * NW) void dec_logits_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// RAGGED (the *_ragged entry points; here and in the two token tails below): the sequences are right-aligned in the caches,
+// sequence b's first token sits at cache position key_start[b], so cache position t is its LOGICAL position t - key_start[b] and
+// the learned positional row is pos[max(0, t - key_start[b])] (a padded position takes row 0: its x is never read by a valid query).
+__device__ __forceinline__ int ragged_pos(int t, const int* __restrict__ key_start, int b) {
+  const int l = t - key_start[b];
+  return l < 0 ? 0 : (l < t ? l : t);  // a negative start cannot index past the cache position
+}
+
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restrict__ tok, const bf16* __restrict__ E,
                                                         const float* __restrict__ pos, const int* __restrict__ pos_ptr,
-                                                        float* __restrict__ x, int B, int d, int V) {
+                                                        float* __restrict__ x, int B, int d, int V,
+                                                        const int* __restrict__ key_start) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
-  const int t = *pos_ptr;
+  const int t = RAGGED ? ragged_pos(*pos_ptr, key_start, row) : *pos_ptr;
   int64_t id = tok[row];
   id = id < 0 ? 0 : (id >= V ? V - 1 : id);
   for (int c = lane; c < d / 8; c += 64) {
@@ -842,21 +852,33 @@ __device__ __forceinline__ float block_reduce(float v, float* scratch, bool is_m
   return r;
 }
 
+// RAGGED (pm_dec_attention_ragged): sequence b attends keys lo .. Lk - 1, lo = min(key_start[b], Lk - 1) - the arithmetic below
+// depends on a key's index relative to the base pointer only, so the base moves up by lo keys and Lk shrinks by lo: the result
+// is pm_dec_attention's on that view of the caches, bit for bit.  A start at or past Lk (a still-padded row) leaves the newest key.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void dec_attn_kernel(const float* __restrict__ q, const bf16* __restrict__ Kc,
                                                        const bf16* __restrict__ Vc, int64_t sb, int64_t sh, int64_t sk,
                                                        const int* __restrict__ lk_ptr, int lk_add, float* __restrict__ out,
-                                                       int H) {
+                                                       int H, const int* __restrict__ key_start) {
   __shared__ float sc[DA_MAXK];
   __shared__ float scratch[4];
   __shared__ float part[4 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
-  const int Lk = (lk_ptr ? *lk_ptr : 0) + lk_add;
+  int Lk = (lk_ptr ? *lk_ptr : 0) + lk_add;
   const int c = lane & 7, ks = lane >> 3;
   const float* qp = q + ((int64_t)b * H + h) * 64 + c * 8;
   const f32x4 q0 = *(const f32x4*)qp, q1 = *(const f32x4*)(qp + 4);
   const bf16* kb = Kc + b * sb + h * sh + c * 8;
   const bf16* vb = Vc + b * sb + h * sh + c * 8;
+  if constexpr (RAGGED) {
+    int lo = key_start[b];
+    lo = lo < Lk - 1 ? lo : Lk - 1;
+    lo = lo < 0 ? 0 : lo;
+    kb += lo * sk;
+    vb += lo * sk;
+    Lk -= lo;
+  }
 
   // ---- scores: 8 lanes per key, 32 keys per workgroup pass
   for (int k0 = 0; k0 < Lk; k0 += 128) {
@@ -1363,6 +1385,7 @@ __global__ __launch_bounds__(DF_THREADS) void dec_attn_fused_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
                                                                 int nwg, const int* __restrict__ pos_ptr,
                                                                 const int64_t* __restrict__ prompt, int P,
@@ -1371,7 +1394,7 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
                                                                 // fused tail (all null / 0 for the plain reduce):
                                                                 const bf16* __restrict__ E, const float* __restrict__ pos_tab,
                                                                 float* __restrict__ x, int d, int V, int* ticket,
-                                                                int* pos_rw) {
+                                                                int* pos_rw, const int* __restrict__ key_start) {
   __shared__ float sv[4];
   __shared__ int si[4];
   __shared__ float s2[4];
@@ -1382,10 +1405,11 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
   const int t = *pos_ptr;  // the token just consumed sits at position t; this step decides position t + 1
   const int t1 = t + 1;
   const int64_t forced = t1 < P ? prompt[(int64_t)b * P + t1] : -1;
+  const int tp = RAGGED ? ragged_pos(t1, key_start, b) : t1;  // the positional row of the next step's x
   f32x4 pp0 = {0.f, 0.f, 0.f, 0.f}, pp1 = pp0;
   if (E && tid < d / 8) {
-    pp0 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + tid * 8);
-    pp1 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + tid * 8 + 4);
+    pp0 = *(const f32x4*)(pos_tab + (int64_t)tp * d + tid * 8);
+    pp1 = *(const f32x4*)(pos_tab + (int64_t)tp * d + tid * 8 + 4);
   }
   float bv = -INFINITY, second = -INFINITY;
   int bi = 0x7fffffff;
@@ -1460,8 +1484,8 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
     const bf16x8 e = *(const bf16x8*)(E + id * d + c * 8);
     f32x4 p0 = pp0, p1 = pp1;
     if (c != tid) {  // d > 2048 only
-      p0 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + c * 8);
-      p1 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + c * 8 + 4);
+      p0 = *(const f32x4*)(pos_tab + (int64_t)tp * d + c * 8);
+      p1 = *(const f32x4*)(pos_tab + (int64_t)tp * d + c * 8 + 4);
     }
     f32x4 o0, o1;
 #pragma unroll
@@ -1567,12 +1591,13 @@ __device__ __forceinline__ float ds_uniform(uint64_t seed, int t, int b) {  // s
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void dec_sample_topk_kernel(const float* __restrict__ logits, int ldl, int V, int k,
                                                               uint64_t seed, const int64_t* __restrict__ prompt, int P,
                                                               int64_t* __restrict__ tok_cur, int64_t* __restrict__ tokens_out,
                                                               int Ttot, const bf16* __restrict__ E,
                                                               const float* __restrict__ pos_tab, float* __restrict__ x, int d,
-                                                              int* ticket, int* pos_rw) {
+                                                              int* ticket, int* pos_rw, const int* __restrict__ key_start) {
   __shared__ float topv[DS_MAXK];
   __shared__ int topi[DS_MAXK];
   __shared__ float wv[4];
@@ -1610,13 +1635,26 @@ __global__ __launch_bounds__(256) void dec_sample_topk_kernel(const float* __res
   }
   const int t = *pos_rw;
   if (tid == 0) {
-    float cum[DS_MAXK];
-    float sum = 0.f;
-    for (int r = 0; r < k; ++r) { sum += expf(topv[r] - topv[0]); cum[r] = sum; }
-    const float u = ds_uniform(seed, t, b) * sum;
     int pick = k - 1;
-    for (int r = k - 1; r >= 0; --r)
-      if (u < cum[r]) pick = r;
+    if constexpr (RAGGED) {
+      // the plain form's draw without its per-thread array (scratch memory): the running sums are formed twice, in the same
+      // order, so the pick is the same
+      float sum = 0.f;
+      for (int r = 0; r < k; ++r) sum += expf(topv[r] - topv[0]);
+      const float u = ds_uniform(seed, t, b) * sum;
+      float cum = 0.f;
+      for (int r = 0; r < k; ++r) {
+        cum += expf(topv[r] - topv[0]);
+        if (u < cum) { pick = r; break; }
+      }
+    } else {
+      float cum[DS_MAXK];
+      float sum = 0.f;
+      for (int r = 0; r < k; ++r) { sum += expf(topv[r] - topv[0]); cum[r] = sum; }
+      const float u = ds_uniform(seed, t, b) * sum;
+      for (int r = k - 1; r >= 0; --r)
+        if (u < cum[r]) pick = r;
+    }
     const int64_t next = (t + 1 < P) ? prompt[(int64_t)b * P + t + 1] : (int64_t)topi[pick];
     tok_cur[b] = next;
     if (t + 1 < Ttot) tokens_out[(int64_t)b * Ttot + t + 1] = next;
@@ -1624,11 +1662,12 @@ __global__ __launch_bounds__(256) void dec_sample_topk_kernel(const float* __res
   }
   __syncthreads();
   const int t1 = t + 1;
+  const int tp = RAGGED ? ragged_pos(t1, key_start, b) : t1;
   int64_t id = snext;
   id = id < 0 ? 0 : (id >= V ? V - 1 : id);
   for (int c = tid; c < d / 8; c += 256) {
     const bf16x8 e = *(const bf16x8*)(E + id * d + c * 8);
-    const f32x4 p0 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + c * 8), p1 = *(const f32x4*)(pos_tab + (int64_t)t1 * d + c * 8 + 4);
+    const f32x4 p0 = *(const f32x4*)(pos_tab + (int64_t)tp * d + c * 8), p1 = *(const f32x4*)(pos_tab + (int64_t)tp * d + c * 8 + 4);
     f32x4 o0, o1;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { o0[i] = (float)e[i] + p0[i]; o1[i] = (float)e[4 + i] + p1[i]; }
@@ -1650,15 +1689,28 @@ __global__ void dec_advance_kernel(int* pos_ptr) { *pos_ptr += 1; }
 }  // namespace
 
 // =================================================================================================================
-extern "C" int pm_dec_embed(const int64_t* tok_cur, const void* emb, const float* pos, const int32_t* pos_ptr, float* x,
-                            int64_t B, int64_t d, int64_t V, void* stream) {
+template <bool RAGGED>
+static int dec_embed_impl(const int64_t* tok_cur, const void* emb, const float* pos, const int32_t* pos_ptr, float* x, int64_t B,
+                          int64_t d, int64_t V, const int32_t* key_start, void* stream) {
   if (!tok_cur || !emb || !pos || !pos_ptr || !x || B <= 0 || d <= 0 || V <= 0) return PM_EINVAL;
   if (d % 8) return PM_EUNSUPPORTED;
   if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)x) & 15) return PM_EALIGN;
-  hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tok_cur,
-                     (const bf16*)emb, pos, (const int*)pos_ptr, x, (int)B, (int)d, (int)V);
+  hipLaunchKernelGGL(dec_embed_kernel<RAGGED>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tok_cur,
+                     (const bf16*)emb, pos, (const int*)pos_ptr, x, (int)B, (int)d, (int)V, (const int*)key_start);
   PM_CHECK_LAUNCH();
   return PM_OK;
+}
+
+extern "C" int pm_dec_embed(const int64_t* tok_cur, const void* emb, const float* pos, const int32_t* pos_ptr, float* x,
+                            int64_t B, int64_t d, int64_t V, void* stream) {
+  return dec_embed_impl<false>(tok_cur, emb, pos, pos_ptr, x, B, d, V, nullptr, stream);
+}
+
+/* pm_dec_embed for right-aligned sequences: x[b] = emb[tok_cur[b]] + pos[max(0, *pos_ptr - key_start[b])] */
+extern "C" int pm_dec_embed_ragged(const int64_t* tok_cur, const void* emb, const float* pos, const int32_t* pos_ptr,
+                                   const int32_t* key_start, float* x, int64_t B, int64_t d, int64_t V, void* stream) {
+  if (!key_start) return PM_EINVAL;
+  return dec_embed_impl<true>(tok_cur, emb, pos, pos_ptr, x, B, d, V, key_start, stream);
 }
 
 #define PM_DL_ARGS                                                                                                   \
@@ -1861,19 +1913,35 @@ extern "C" int pm_dec_linear_kparts(const float* x, int64_t ldx, const void* w, 
 /* features per argmax tile for a given K (callers size ws_val / ws_idx as ceil(N / tile)) */
 extern "C" int pm_dec_argmax_tile(int64_t K) { return ((K / 32 + 3) / 4 > 4) ? 32 : 64; }
 
-extern "C" int pm_dec_attention(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h,
-                                int64_t stride_k, const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max, float* out,
-                                int64_t B, int64_t H, void* stream) {
+template <bool RAGGED>
+static int dec_attention_impl(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h, int64_t stride_k,
+                              const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max, const int32_t* key_start, float* out,
+                              int64_t B, int64_t H, void* stream) {
   if (!q || !kc || !vc || !out || B <= 0 || H <= 0 || lk_add < 0 || lk_max <= 0) return PM_EINVAL;
   if (lk_max > DA_MAXK) return PM_EUNSUPPORTED;
   if (!lk_ptr && lk_add <= 0) return PM_EINVAL;
   if ((stride_b | stride_h | stride_k) % 8) return PM_EALIGN;
   if (((uintptr_t)q | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)out) & 15) return PM_EALIGN;
   if (B * H > 0x7fffffff) return PM_EINVAL;
-  hipLaunchKernelGGL(dec_attn_kernel, dim3((unsigned)(B * H)), dim3(256), 0, (hipStream_t)stream, q, (const bf16*)kc,
-                     (const bf16*)vc, stride_b, stride_h, stride_k, (const int*)lk_ptr, (int)lk_add, out, (int)H);
+  hipLaunchKernelGGL(dec_attn_kernel<RAGGED>, dim3((unsigned)(B * H)), dim3(256), 0, (hipStream_t)stream, q, (const bf16*)kc,
+                     (const bf16*)vc, stride_b, stride_h, stride_k, (const int*)lk_ptr, (int)lk_add, out, (int)H,
+                     (const int*)key_start);
   PM_CHECK_LAUNCH();
   return PM_OK;
+}
+
+extern "C" int pm_dec_attention(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h,
+                                int64_t stride_k, const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max, float* out,
+                                int64_t B, int64_t H, void* stream) {
+  return dec_attention_impl<false>(q, kc, vc, stride_b, stride_h, stride_k, lk_ptr, lk_add, lk_max, nullptr, out, B, H, stream);
+}
+
+/* pm_dec_attention over the keys min(key_start[b], Lk - 1) .. Lk - 1 of sequence b (key_start: int32, B of them, on the device) */
+extern "C" int pm_dec_attention_ragged(const float* q, const void* kc, const void* vc, int64_t stride_b, int64_t stride_h,
+                                       int64_t stride_k, const int32_t* lk_ptr, int64_t lk_add, int64_t lk_max,
+                                       const int32_t* key_start, float* out, int64_t B, int64_t H, void* stream) {
+  if (!key_start) return PM_EINVAL;
+  return dec_attention_impl<true>(q, kc, vc, stride_b, stride_h, stride_k, lk_ptr, lk_add, lk_max, key_start, out, B, H, stream);
 }
 
 template <typename KT, bool CHAIN>
@@ -1952,10 +2020,10 @@ extern "C" int pm_dec_argmax_reduce(const float* ws_val, const int32_t* ws_idx, 
                                     int64_t Ttot, float* margin_out, int64_t B, void* stream) {
   if (!ws_val || !ws_idx || !pos_ptr || !prompt || !tok_cur || !tokens_out || n_tiles <= 0 || P <= 0 || B <= 0 || Ttot < P)
     return PM_EINVAL;
-  hipLaunchKernelGGL(dec_argmax_reduce_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, ws_val,
+  hipLaunchKernelGGL(dec_argmax_reduce_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, ws_val,
                      (const int*)ws_idx, (int)n_tiles, (const int*)pos_ptr, prompt, (int)P, tok_cur, tokens_out, (int)Ttot,
                      margin_out, (const bf16*)nullptr, (const float*)nullptr, (float*)nullptr, 0, 0, (int*)nullptr,
-                     (int*)nullptr);
+                     (int*)nullptr, (const int*)nullptr);
   PM_CHECK_LAUNCH();
   return PM_OK;
 }
@@ -1964,20 +2032,40 @@ extern "C" int pm_dec_argmax_reduce(const float* ws_val, const int32_t* ws_idx, 
  * its token, writes x[b] = emb[token] + pos[t + 1], and the last workgroup to finish (agent-scope ticket, left at 0)
  * stores t + 1 to *pos_ptr.  Before the first step of a run the caller sets *pos_ptr = 0, tok_cur and runs
  * pm_dec_embed once. */
-extern "C" int pm_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr,
-                                 const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
-                                 float* margin_out, const void* emb, const float* pos, float* x, int64_t d, int64_t V,
-                                 int32_t* ticket, int64_t B, void* stream) {
+template <bool RAGGED>
+static int dec_next_token_impl(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr, const int64_t* prompt,
+                               int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot, float* margin_out, const void* emb,
+                               const float* pos, const int32_t* key_start, float* x, int64_t d, int64_t V, int32_t* ticket,
+                               int64_t B, void* stream) {
   if (!ws_val || !ws_idx || !pos_ptr || !prompt || !tok_cur || !tokens_out || n_tiles <= 0 || P <= 0 || B <= 0 || Ttot < P)
     return PM_EINVAL;
   if (!emb || !pos || !x || !ticket || d <= 0 || V <= 0) return PM_EINVAL;
   if (d % 8) return PM_EUNSUPPORTED;
   if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)x) & 15) return PM_EALIGN;
-  hipLaunchKernelGGL(dec_argmax_reduce_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, ws_val,
+  hipLaunchKernelGGL(dec_argmax_reduce_kernel<RAGGED>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, ws_val,
                      (const int*)ws_idx, (int)n_tiles, (const int*)pos_ptr, prompt, (int)P, tok_cur, tokens_out, (int)Ttot,
-                     margin_out, (const bf16*)emb, pos, x, (int)d, (int)V, (int*)ticket, (int*)pos_ptr);
+                     margin_out, (const bf16*)emb, pos, x, (int)d, (int)V, (int*)ticket, (int*)pos_ptr, (const int*)key_start);
   PM_CHECK_LAUNCH();
   return PM_OK;
+}
+
+extern "C" int pm_dec_next_token(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr,
+                                 const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                                 float* margin_out, const void* emb, const float* pos, float* x, int64_t d, int64_t V,
+                                 int32_t* ticket, int64_t B, void* stream) {
+  return dec_next_token_impl<false>(ws_val, ws_idx, n_tiles, pos_ptr, prompt, P, tok_cur, tokens_out, Ttot, margin_out, emb, pos,
+                                    nullptr, x, d, V, ticket, B, stream);
+}
+
+/* pm_dec_next_token for right-aligned sequences (prompt = the right-aligned prompt matrix): the next step's row is
+ * x[b] = emb[token] + pos[max(0, t + 1 - key_start[b])]; token choice, prompt forcing, margins and the ticketed advance unchanged */
+extern "C" int pm_dec_next_token_ragged(const float* ws_val, const int32_t* ws_idx, int64_t n_tiles, int32_t* pos_ptr,
+                                        const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                                        float* margin_out, const void* emb, const float* pos, const int32_t* key_start, float* x,
+                                        int64_t d, int64_t V, int32_t* ticket, int64_t B, void* stream) {
+  if (!key_start) return PM_EINVAL;
+  return dec_next_token_impl<true>(ws_val, ws_idx, n_tiles, pos_ptr, prompt, P, tok_cur, tokens_out, Ttot, margin_out, emb, pos,
+                                   key_start, x, d, V, ticket, B, stream);
 }
 
 extern "C" int pm_dec_whisper_rules(float* logits, int64_t ldl, int64_t V, const int64_t* tokens, int64_t Ttot,
@@ -1998,19 +2086,39 @@ extern "C" int pm_dec_whisper_rules(float* logits, int64_t ldl, int64_t V, const
  * the k (1..64) largest per row (ties: lowest index first), softmax over them, one draw per sequence from a
  * counter-based generator keyed by (seed, position, sequence); then pm_dec_next_token's tail (prompt forcing, the next
  * step's embedding row, ticketed position advance).  k = 1 is the arg-max. */
-extern "C" int pm_dec_sample_topk(const float* logits, int64_t ldl, int64_t V, int64_t k, uint64_t seed, int32_t* pos_ptr,
-                                  const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
-                                  const void* emb, const float* pos, float* x, int64_t d, int32_t* ticket, int64_t B,
-                                  void* stream) {
+template <bool RAGGED>
+static int dec_sample_topk_impl(const float* logits, int64_t ldl, int64_t V, int64_t k, uint64_t seed, int32_t* pos_ptr,
+                                const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                                const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d, int32_t* ticket,
+                                int64_t B, void* stream) {
   if (!logits || !pos_ptr || !prompt || !tok_cur || !tokens_out || !emb || !pos || !x || !ticket) return PM_EINVAL;
   if (V <= 0 || ldl < V || k < 1 || k > DS_MAXK || k > V || P <= 0 || B <= 0 || Ttot < P || d <= 0) return PM_EINVAL;
   if (d % 8) return PM_EUNSUPPORTED;
   if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)x) & 15) return PM_EALIGN;
-  hipLaunchKernelGGL(dec_sample_topk_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, (int)ldl, (int)V,
+  hipLaunchKernelGGL(dec_sample_topk_kernel<RAGGED>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, (int)ldl, (int)V,
                      (int)k, seed, prompt, (int)P, tok_cur, tokens_out, (int)Ttot, (const bf16*)emb, pos, x, (int)d,
-                     (int*)ticket, (int*)pos_ptr);
+                     (int*)ticket, (int*)pos_ptr, (const int*)key_start);
   PM_CHECK_LAUNCH();
   return PM_OK;
+}
+
+extern "C" int pm_dec_sample_topk(const float* logits, int64_t ldl, int64_t V, int64_t k, uint64_t seed, int32_t* pos_ptr,
+                                  const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                                  const void* emb, const float* pos, float* x, int64_t d, int32_t* ticket, int64_t B,
+                                  void* stream) {
+  return dec_sample_topk_impl<false>(logits, ldl, V, k, seed, pos_ptr, prompt, P, tok_cur, tokens_out, Ttot, emb, pos, nullptr, x,
+                                     d, ticket, B, stream);
+}
+
+/* pm_dec_sample_topk for right-aligned sequences: the tail's positional row is pos[max(0, t + 1 - key_start[b])]; the draw stays
+ * keyed by (seed, CACHE position, sequence) */
+extern "C" int pm_dec_sample_topk_ragged(const float* logits, int64_t ldl, int64_t V, int64_t k, uint64_t seed, int32_t* pos_ptr,
+                                         const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                                         const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d,
+                                         int32_t* ticket, int64_t B, void* stream) {
+  if (!key_start) return PM_EINVAL;
+  return dec_sample_topk_impl<true>(logits, ldl, V, k, seed, pos_ptr, prompt, P, tok_cur, tokens_out, Ttot, emb, pos, key_start, x,
+                                    d, ticket, B, stream);
 }
 
 extern "C" int pm_dec_advance(int32_t* pos_ptr, void* stream) {

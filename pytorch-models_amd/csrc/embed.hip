@@ -5,16 +5,22 @@
 
 namespace {
 
-template <bool YF32, typename ET = bf16>
+// RAGGED (pm_embed_tokens_ragged): sequence b is right-aligned, its first token at position key_start[b] - the positional row of
+// position pos0 + l is pos[max(0, pos0 + l - key_start[b])]
+template <bool YF32, typename ET = bf16, bool RAGGED = false>
 __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ tok, const ET* __restrict__ E,
                                                     const float* __restrict__ pos, void* __restrict__ out, int64_t rows,
-                                                    int L, int pos0, int d, int V) {
+                                                    int L, int pos0, int d, int V, const int* __restrict__ key_start) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   int64_t t = tok[row];
   t = t < 0 ? 0 : (t >= V ? V - 1 : t);  // ops.embed_tokens raises on ids outside [0, V); clamp so that a raw C-ABI caller's bad id cannot fault
-  const int l = (int)(row % L) + pos0;
+  int l = (int)(row % L) + pos0;
+  if constexpr (RAGGED) {
+    const int ll = l - key_start[row / L];
+    l = ll < 0 ? 0 : (ll < l ? ll : l);
+  }
   for (int c = lane; c < d / 8; c += 64) {
     float e[8];
     if constexpr (sizeof(ET) == 2) {
@@ -58,10 +64,32 @@ extern "C" int pm_embed_tokens(const int64_t* tokens, const void* emb, const flo
   if (nblk > 0x7fffffff) return PM_EINVAL;
   if (out_dtype == PM_F32)
     hipLaunchKernelGGL((embed_kernel<true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tokens,
-                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V);
+                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V, (const int*)nullptr);
   else if (out_dtype == PM_BF16)
     hipLaunchKernelGGL((embed_kernel<false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tokens,
-                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V);
+                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V, (const int*)nullptr);
+  else
+    return PM_EINVAL;
+  PM_CHECK_LAUNCH();
+  return PM_OK;
+}
+
+/* pm_embed_tokens for right-aligned sequences (the prompt pass of ragged batches): out[b, l] = emb[tok] + pos[max(0, pos0 + l -
+ * key_start[b])]; key_start int32, B of them, on the device; the positional table is required. */
+extern "C" int pm_embed_tokens_ragged(const int64_t* tokens, const void* emb, const float* pos, const int32_t* key_start, void* out,
+                                      int out_dtype, int64_t B, int64_t L, int64_t pos0, int64_t d, int64_t V, void* stream) {
+  if (!tokens || !emb || !pos || !key_start || !out || B < 0 || L < 0 || d <= 0 || V <= 0 || pos0 < 0) return PM_EINVAL;
+  if (B == 0 || L == 0) return PM_OK;
+  if (d % 8) return PM_EUNSUPPORTED;
+  if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)out) & 15) return PM_EALIGN;
+  const int64_t rows = B * L, nblk = (rows + 3) / 4;
+  if (nblk > 0x7fffffff || pos0 + L > 0x7fffffff) return PM_EINVAL;
+  if (out_dtype == PM_F32)
+    hipLaunchKernelGGL((embed_kernel<true, bf16, true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tokens,
+                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V, (const int*)key_start);
+  else if (out_dtype == PM_BF16)
+    hipLaunchKernelGGL((embed_kernel<false, bf16, true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tokens,
+                       (const bf16*)emb, pos, out, rows, (int)L, (int)pos0, (int)d, (int)V, (const int*)key_start);
   else
     return PM_EINVAL;
   PM_CHECK_LAUNCH();
@@ -78,7 +106,7 @@ extern "C" int pm_embed_tokens_f32(const int64_t* tokens, const float* emb, cons
   const int64_t rows = B * L, nblk = (rows + 3) / 4;
   if (nblk > 0x7fffffff) return PM_EINVAL;
   hipLaunchKernelGGL((embed_kernel<true, float>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tokens, emb, pos,
-                     (void*)out, rows, (int)L, (int)pos0, (int)d, (int)V);
+                     (void*)out, rows, (int)L, (int)pos0, (int)d, (int)V, (const int*)nullptr);
   PM_CHECK_LAUNCH();
   return PM_OK;
 }

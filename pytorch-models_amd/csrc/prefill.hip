@@ -34,9 +34,17 @@ constexpr int PF_QB = 16 * PF_WAVES;  // queries per workgroup
 constexpr int PF_KT = 64;             // keys per tile
 constexpr int PF_VLD = 68;            // bf16 per dim row of the transposed V tile (64 keys + 4: 8-byte aligned, skews banks)
 
+// RAGGED (pm_prefill_attention_ragged_bf16): sequence b's keys below key_start[b] are padding.  The query at position p keeps
+// the keys lo(p) <= j <= p, lo(p) = min(key_start[b], p): a padded query (p < key_start[b]) sees itself only, so "key p is visible
+// to query p" takes the place of "key 0 is visible to every query".  lo() does not decrease with p, so a wave's lowest lo is its
+// first query's and the workgroup's its first row's: the walk starts at the tile that holds the workgroup's lowest lo, and a wave
+// skips the tiles wholly below its own (wave-uniform, like the tiles behind the causal mask).  A query whose lo lies in a later
+// tile than its wave's first meets fully masked tiles BEFORE its first visible key: its running maximum is still -inf there, and
+// the exponentials are then taken against 0 instead (p = 0, alpha = 0, nothing accumulated).  The append is the plain kernel's.
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * PF_WAVES) void prefill_attention_kernel(
     const bf16* __restrict__ QKV, int64_t ld, bf16* KC, bf16* VC, int64_t sb, int64_t sh, int64_t sk, bf16* __restrict__ O,
-    int64_t ldo, int H, int C, int p0, float scale_log2) {
+    int64_t ldo, int H, int C, int p0, float scale_log2, const int* __restrict__ key_start) {
   __shared__ __attribute__((aligned(16))) bf16 vt[2][64 * PF_VLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
@@ -72,6 +80,15 @@ __global__ __launch_bounds__(64 * PF_WAVES) void prefill_attention_kernel(
   for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(Qb + (int64_t)qic * ld + 32 * ks + g * 8);
   const int qpos = p0 + qic;  // the last key this lane's query sees
   const int wave_last = p0 + (q0 + 15 < C ? q0 + 15 : C - 1);  // the last key any query of the wave sees (q0 >= C: the last row's)
+  int qlo = 0, wave_lo = 0, t0 = 0;  // the first key this lane's query sees, the lowest of the wave's, the workgroup's first tile
+  if constexpr (RAGGED) {
+    int ks = key_start[b];
+    ks = ks < 0 ? 0 : ks;
+    qlo = ks < qpos ? ks : qpos;
+    const int wfirst = p0 + (q0 < C ? q0 : C - 1);
+    wave_lo = ks < wfirst ? ks : wfirst;
+    t0 = (ks < p0 + i0 ? ks : p0 + i0) / PF_KT;
+  }
 
   const int nkeys = p0 + (i0 + PF_QB < C ? i0 + PF_QB : C);  // keys 0 .. nkeys - 1 are visible to some query of the workgroup
   const int ntiles = (nkeys + PF_KT - 1) / PF_KT;
@@ -116,9 +133,9 @@ __global__ __launch_bounds__(64 * PF_WAVES) void prefill_attention_kernel(
   for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
 
-  load_tile(0);
-  store_v(0);
-  for (int t = 0; t < ntiles; ++t) {
+  load_tile(t0);
+  store_v(t0 & 1);
+  for (int t = t0; t < ntiles; ++t) {
     const int buf = t & 1;
     bf16x8 kc[4][2];
 #pragma unroll
@@ -129,7 +146,7 @@ __global__ __launch_bounds__(64 * PF_WAVES) void prefill_attention_kernel(
     if (t + 1 < ntiles) load_tile(t + 1);
 
     const int k0 = t * PF_KT;
-    if (k0 <= wave_last) {  // wave-uniform: a tile wholly behind the wave's mask adds nothing
+    if (k0 <= wave_last && (!RAGGED || k0 + PF_KT > wave_lo)) {  // wave-uniform: a tile wholly behind the wave's mask adds nothing
       f32x4 s[4];
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
@@ -143,20 +160,24 @@ __global__ __launch_bounds__(64 * PF_WAVES) void prefill_attention_kernel(
         for (int i = 0; i < 4; ++i) {
           float v = s[kb][i] * scale_log2;
           if (k0 + 16 * kb + 4 * g + i > qpos) v = -INFINITY;  // causal on absolute positions (covers keys >= nkeys too)
+          if constexpr (RAGGED)
+            if (k0 + 16 * kb + 4 * g + i < qlo) v = -INFINITY;  // the sequence's padding
           s[kb][i] = v;
           m = fmaxf(m, v);
         }
       }
       m = fmaxf(m, __shfl_xor(m, 16, 64));
       m = fmaxf(m, __shfl_xor(m, 32, 64));
-      const float m_new = fmaxf(m_run, m);       // finite: key 0 is in tile 0 and visible to every query
-      const float alpha = exp2f(m_run - m_new);  // first tile: exp2(-inf) = 0
+      const float m_new = fmaxf(m_run, m);  // plain: finite, key 0 is in tile 0 and visible to every query
+      // ragged: -inf until the tile of the query's first visible key - exponentials against 0 there (all of them exp2(-inf) = 0)
+      const float m_ref = (RAGGED && m_new == -INFINITY) ? 0.f : m_new;
+      const float alpha = exp2f(m_run - m_ref);  // first tile: exp2(-inf) = 0
       float sum = 0.f;
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float p = exp2f(s[kb][i] - m_new);
+          const float p = exp2f(s[kb][i] - m_ref);
           s[kb][i] = p;
           sum += p;
         }
@@ -203,9 +224,10 @@ bool pf_aligned(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(b
 
 }  // namespace
 
-extern "C" int pm_prefill_attention_bf16(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b, int64_t stride_h,
-                                         int64_t stride_k, void* out, int64_t ld_out, int64_t B, int64_t H, int64_t C, int64_t p0,
-                                         int64_t lk_max, void* stream) {
+template <bool RAGGED>
+static int prefill_attention_impl(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b, int64_t stride_h,
+                                  int64_t stride_k, void* out, int64_t ld_out, int64_t B, int64_t H, int64_t C, int64_t p0,
+                                  int64_t lk_max, const int32_t* key_start, void* stream) {
   // every refusal is PM_EINVAL and comes before any HIP call
   if (!qkv || !kc || !vc || !out || B < 0 || H < 1 || C < 1 || p0 < 0) return PM_EINVAL;
   if (lk_max > 4096 || p0 + C > lk_max || H > 4096 || B * H > 65535) return PM_EINVAL;
@@ -215,8 +237,27 @@ extern "C" int pm_prefill_attention_bf16(const void* qkv, int64_t ld_qkv, void* 
   if (B == 0) return PM_OK;
   const float scale_log2 = 0.125f * 1.4426950408889634f;  // 1 / sqrt(64) * log2(e)
   const dim3 grid((unsigned)((C + PF_QB - 1) / PF_QB), (unsigned)(B * H));
-  hipLaunchKernelGGL(prefill_attention_kernel, grid, dim3(64 * PF_WAVES), 0, (hipStream_t)stream, (const bf16*)qkv, ld_qkv, (bf16*)kc,
-                     (bf16*)vc, stride_b, stride_h, stride_k, (bf16*)out, ld_out, (int)H, (int)C, (int)p0, scale_log2);
+  hipLaunchKernelGGL(prefill_attention_kernel<RAGGED>, grid, dim3(64 * PF_WAVES), 0, (hipStream_t)stream, (const bf16*)qkv, ld_qkv,
+                     (bf16*)kc, (bf16*)vc, stride_b, stride_h, stride_k, (bf16*)out, ld_out, (int)H, (int)C, (int)p0, scale_log2,
+                     (const int*)key_start);
   PM_CHECK_LAUNCH();
   return PM_OK;
+}
+
+extern "C" int pm_prefill_attention_bf16(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b, int64_t stride_h,
+                                         int64_t stride_k, void* out, int64_t ld_out, int64_t B, int64_t H, int64_t C, int64_t p0,
+                                         int64_t lk_max, void* stream) {
+  return prefill_attention_impl<false>(qkv, ld_qkv, kc, vc, stride_b, stride_h, stride_k, out, ld_out, B, H, C, p0, lk_max, nullptr,
+                                       stream);
+}
+
+/* pm_prefill_attention_bf16 for sequences right-aligned in the caches: sequence b's keys below key_start[b] (int32, B of them, on
+ * the device) are padding - see prefill_attention_kernel<true>.  key_start all zero is pm_prefill_attention_bf16 bit for bit. */
+extern "C" int pm_prefill_attention_ragged_bf16(const void* qkv, int64_t ld_qkv, void* kc, void* vc, int64_t stride_b,
+                                                int64_t stride_h, int64_t stride_k, void* out, int64_t ld_out, int64_t B,
+                                                int64_t H, int64_t C, int64_t p0, int64_t lk_max, const int32_t* key_start,
+                                                void* stream) {
+  if (!key_start) return PM_EINVAL;
+  return prefill_attention_impl<true>(qkv, ld_qkv, kc, vc, stride_b, stride_h, stride_k, out, ld_out, B, H, C, p0, lk_max, key_start,
+                                      stream);
 }

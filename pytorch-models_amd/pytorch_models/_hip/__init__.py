@@ -58,6 +58,12 @@ SIGNATURES = {
     "pm_dec_beam_topw": ([_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _l, _p], c_int),
     "pm_dec_beam_select": ([_p, _p, _l, _p, _p, _p, _l, _p, _l, _p, _p, _l, _p, _p, _p, _p, _l, _l, _p, _l, _p], c_int),
     "pm_dec_beam_reorder": ([_p, _l, _p, _p, _l, _l, _l, _l, _i, _p], c_int),
+    "pm_dec_attention_ragged": ([_p, _p, _p, _l, _l, _l, _p, _l, _l, _p, _p, _l, _l, _p], c_int),
+    "pm_prefill_attention_ragged_bf16": ([_p, _l, _p, _p, _l, _l, _l, _p, _l, _l, _l, _l, _l, _l, _p, _p], c_int),
+    "pm_embed_tokens_ragged": ([_p, _p, _p, _p, _p, _i, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_dec_embed_ragged": ([_p, _p, _p, _p, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_dec_next_token_ragged": ([_p, _p, _l, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _l, _l, _p, _l, _p], c_int),
+    "pm_dec_sample_topk_ragged": ([_p, _l, _l, _l, ctypes.c_uint64, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _l, _p, _l, _p], c_int),
     "pm_layernorm": ([_p, _l, _i, _p, _p, _f, _p, _l, _i, _l, _l, _p], c_int),
     "pm_layernorm_ex": ([_p, _l, _i, _p, _p, _f, _i, _p, _l, _i, _p, _l, _i, _l, _l, _p], c_int),
     "pm_rmsnorm": ([_p, _l, _i, _p, _f, _p, _l, _i, _l, _l, _p], c_int),

@@ -99,6 +99,45 @@ def prefill_attention_args(qkv: Tensor, kv: KV, out: Tensor, rows: int, heads: i
             heads, chunk, p0, lk_max, None)
 
 
+# ---- ragged prompt batches: the sequences are right-aligned in the caches and ``key_start`` (int32 (rows,), on the device) holds
+# each one's first cache position; every builder is its plain namesake plus that pointer (include/pm_mi355x.h) ----
+def ragged_attention_args(q: Tensor, kv: KV, out: Tensor, rows: int, heads: int, *, pos: Tensor | None, lk_add: int, lk_max: int,
+                          key_start: Tensor) -> tuple:
+    """pm_dec_attention_ragged: row b attends keys min(key_start[b], Lk - 1) .. Lk - 1 of its (*pos if pos else 0) + lk_add keys"""
+    return (q.data_ptr(), *kv, ptr(pos), lk_add, lk_max, key_start.data_ptr(), out.data_ptr(), rows, heads, None)
+
+
+def ragged_prefill_attention_args(qkv: Tensor, kv: KV, out: Tensor, rows: int, heads: int, chunk: int, p0: int, lk_max: int,
+                                  key_start: Tensor) -> tuple:
+    """pm_prefill_attention_ragged_bf16: prefill_attention_args with the keys below key_start[b] masked"""
+    return (*prefill_attention_args(qkv, kv, out, rows, heads, chunk, p0, lk_max)[:-1], key_start.data_ptr(), None)
+
+
+def ragged_embed_args(tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, pos: Tensor, key_start: Tensor, x: Tensor) -> tuple:
+    """pm_dec_embed_ragged: x[b] = emb[tok_cur[b]] + pos_tab[max(0, *pos - key_start[b])]"""
+    V, d = emb.shape
+    return (tok_cur.data_ptr(), emb.data_ptr(), pos_tab.data_ptr(), pos.data_ptr(), key_start.data_ptr(), x.data_ptr(), x.shape[0], d, V,
+            None)
+
+
+def ragged_next_token_args(ws_val: Tensor, ws_idx: Tensor, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor,
+                           margins: Tensor | None, emb: Tensor, pos_tab: Tensor, key_start: Tensor, x: Tensor, ticket: Tensor) -> tuple:
+    """pm_dec_next_token_ragged: ``prompt`` is the right-aligned (rows, P) matrix"""
+    V, d = emb.shape
+    return (ws_val.data_ptr(), ws_idx.data_ptr(), ws_val.shape[1], pos.data_ptr(), prompt.data_ptr(), prompt.shape[1], tok_cur.data_ptr(),
+            tokens.data_ptr(), tokens.shape[1], ptr(margins), emb.data_ptr(), pos_tab.data_ptr(), key_start.data_ptr(), x.data_ptr(), d,
+            V, ticket.data_ptr(), x.shape[0], None)
+
+
+def ragged_sample_topk_args(logits: Tensor, k: int, seed: int, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor,
+                            emb: Tensor, pos_tab: Tensor, key_start: Tensor, x: Tensor, ticket: Tensor) -> tuple:
+    """pm_dec_sample_topk_ragged: the draw stays keyed by (seed, cache position, row)"""
+    V, d = emb.shape
+    return (logits.data_ptr(), logits.stride(0), V, k, int(seed) & (2**64 - 1), pos.data_ptr(), prompt.data_ptr(), prompt.shape[1],
+            tok_cur.data_ptr(), tokens.data_ptr(), tokens.shape[1], emb.data_ptr(), pos_tab.data_ptr(), key_start.data_ptr(),
+            x.data_ptr(), d, ticket.data_ptr(), x.shape[0], None)
+
+
 def fused_args(x: Tensor, ln, w: Tensor, bias, kv: KV, out: Tensor, rows: int, heads: int, *, self_attn: bool, pos=None,
                n_keys: int) -> tuple:
     """pm_dec_attention_fused / _fused_kv32 / _fused_v2: LayerNorm + projection (+ cache append) + attention, self or cross"""

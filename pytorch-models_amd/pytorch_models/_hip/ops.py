@@ -703,6 +703,143 @@ def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int
     return out
 
 
+# ---- ragged prompt batches (right-aligned sequences, key_start int32 (B,) on the device): eager wrappers for the tests; the
+# decoder builds the same launches through decode_plan's ragged_* builders ----
+def _key_start(key_start: Tensor, B: int, what: str) -> None:
+    _need(key_start.dtype == torch.int32 and key_start.shape == (B,) and key_start.is_contiguous(), f"{what}: key_start must be int32 ({B},)")
+
+
+def dec_attention_ragged(q: Tensor, k: Tensor, v: Tensor, lk: int, key_start: Tensor) -> Tensor:
+    """dec_attention over keys min(key_start[b], lk - 1) .. lk - 1 of row b (pm_dec_attention_ragged)."""
+    _cuda(q, k, v, key_start)
+    B, H, T, _ = k.shape
+    _key_start(key_start, B, "dec_attention_ragged")
+    _need(1 <= lk <= T, "dec_attention_ragged: 1 <= lk <= cache length")
+    out = torch.empty_like(q)
+    plan.call(lib().pm_dec_attention_ragged, plan.ragged_attention_args(q, plan.cache_kv(k, v), out, B, H, pos=None, lk_add=lk, lk_max=T,
+                                                                       key_start=key_start), _stream())
+    return out
+
+
+def prefill_attention_ragged(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int, key_start: Tensor,
+                             out: Tensor | None = None) -> Tensor:
+    """pm_prefill_attention_ragged_bf16: prefill_attention whose query at position p of row b keeps keys min(key_start[b], p) .. p."""
+    _cuda(qkv, kc, vc, out, key_start)
+    _need(kc.dim() == 4 and kc.shape[3] == 64 and kc.shape[1] == n_heads and vc.shape == kc.shape and vc.stride() == kc.stride()
+          and kc.stride(3) == 1, "prefill_attention_ragged: caches must be (B, H, T, 64) with one layout and unit last stride")
+    B, H, T, _ = kc.shape
+    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1 and B > 0 and qkv.shape[0] % B == 0 and qkv.shape[0] > 0,
+          "prefill_attention_ragged: qkv must be (B * C, 3 * H * 64) rows with unit last stride, C >= 1")
+    for t in (qkv, kc, vc):
+        _need(t.dtype == torch.bfloat16, "prefill_attention_ragged: bf16 operands")
+    _key_start(key_start, B, "prefill_attention_ragged")
+    C = qkv.shape[0] // B
+    _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention_ragged: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
+    if out is None:
+        out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention_ragged: out must be bf16 (B * C, H * 64)")
+    kv = plan.cache_kv(kc, vc)
+    rc = _launch("prefill_attention_ragged", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_ragged_bf16(
+        *plan.ragged_prefill_attention_args(qkv, kv, out, B, H, C, p0, T, key_start)[:-1], _stream()))
+    check(rc, f"pm_prefill_attention_ragged_bf16(B={B}, H={H}, C={C}, p0={p0})")
+    return out
+
+
+def embed_tokens_ragged(tokens: Tensor, emb: Tensor, pos: Tensor, key_start: Tensor, pos0: int = 0,
+                        out_dtype: torch.dtype = torch.bfloat16, out: Tensor | None = None) -> Tensor:
+    """tokens int64 (B, L) -> (B, L, d): emb[tokens[b, l]] + pos[max(0, pos0 + l - key_start[b])] (bf16 table)."""
+    _cuda(tokens, emb, pos, out, key_start)
+    _need(tokens.dim() == 2 and tokens.dtype == torch.int64, "embed_tokens_ragged: tokens must be int64 (B, L)")
+    tokens = tokens.contiguous()
+    B, L = tokens.shape
+    V, d = emb.shape
+    _need(emb.dtype == torch.bfloat16 and emb.is_contiguous(), "embed_tokens_ragged: emb bf16 (V, d)")
+    _key_start(key_start, B, "embed_tokens_ragged")
+    if EMBED_CHECK_IDS and tokens.numel() and not torch.cuda.is_current_stream_capturing():
+        if bool(((tokens < 0) | (tokens >= V)).any()):
+            bad = tokens[(tokens < 0) | (tokens >= V)][0].item()
+            raise IndexError(f"embed_tokens_ragged: token id {bad} outside the vocabulary [0, {V})")
+    _need(pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d and pos.shape[0] >= pos0 + L,
+          f"embed_tokens_ragged: need {pos0 + L} position rows, have {pos.shape[0]}")
+    if out is None:
+        out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
+    _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens_ragged: out must be contiguous (B, L, d)")
+    rc = lib().pm_embed_tokens_ragged(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr(), key_start.data_ptr(), out.data_ptr(), _dt(out),
+                                      B, L, pos0, d, V, _stream())
+    check(rc, f"pm_embed_tokens_ragged(B={B}, L={L}, d={d})")
+    return out
+
+
+def dec_embed_ragged(tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, pos: Tensor, key_start: Tensor) -> Tensor:
+    """x (B, d) f32: emb[tok_cur[b]] + pos_tab[max(0, pos - key_start[b])]; pos = the int32 (1,) device position."""
+    _cuda(tok_cur, emb, pos_tab, pos, key_start)
+    B = tok_cur.shape[0]
+    _key_start(key_start, B, "dec_embed_ragged")
+    _need(emb.dtype == torch.bfloat16 and pos_tab.dtype == torch.float32 and pos.dtype == torch.int32 and tok_cur.dtype == torch.int64,
+          "dec_embed_ragged: bf16 table, f32 positions, int32 position, int64 tokens")
+    _need(0 <= int(pos) < pos_tab.shape[0], "dec_embed_ragged: position outside the positional table")
+    x = torch.empty(B, emb.shape[1], dtype=torch.float32, device=emb.device)
+    plan.call(lib().pm_dec_embed_ragged, plan.ragged_embed_args(tok_cur, emb, pos_tab, pos, key_start, x), _stream())
+    return x
+
+
+def _tail_state(what: str, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor, emb: Tensor, pos_tab: Tensor, ticket: Tensor) -> None:
+    B = prompt.shape[0]
+    _need(pos.dtype == torch.int32 and ticket.dtype == torch.int32 and pos.numel() == 1 and ticket.numel() == 1, f"{what}: int32 position and ticket")
+    _need(prompt.dtype == torch.int64 and prompt.is_contiguous() and tokens.dtype == torch.int64 and tokens.is_contiguous()
+          and tokens.shape[0] == B and tokens.shape[1] >= prompt.shape[1] and tok_cur.dtype == torch.int64 and tok_cur.shape == (B,),
+          f"{what}: int64 prompt (B, P), tokens (B, Ttot >= P), tok_cur (B,)")
+    _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
+          and pos_tab.shape[1] == emb.shape[1] and 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: bf16 table, f32 positions covering position + 1")
+
+
+def dec_next_token(ws_val: Tensor, ws_idx: Tensor, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor, emb: Tensor,
+                   pos_tab: Tensor, ticket: Tensor, *, margins: Tensor | None = None, key_start: Tensor | None = None) -> Tensor:
+    """pm_dec_next_token (key_start None) or pm_dec_next_token_ragged on explicit state: picks the token after position *pos from the
+    per-tile (max, index) pairs ws_val / ws_idx (B, n_tiles), updates tok_cur, tokens, margins, pos and ticket IN PLACE and returns
+    the next step's rows x (B, d) f32."""
+    _cuda(ws_val, ws_idx, pos, prompt, tok_cur, tokens, emb, pos_tab, ticket, margins, key_start)
+    _tail_state("dec_next_token", pos, prompt, tok_cur, tokens, emb, pos_tab, ticket)
+    B, P = prompt.shape
+    V, d = emb.shape
+    _need(ws_val.dtype == torch.float32 and ws_idx.dtype == torch.int32 and ws_val.shape == ws_idx.shape and ws_val.shape[0] == B
+          and ws_val.is_contiguous() and ws_idx.is_contiguous(), "dec_next_token: ws_val f32 / ws_idx int32 (B, n_tiles)")
+    _need(margins is None or (margins.dtype == torch.float32 and margins.shape == tokens.shape and margins.is_contiguous()),
+          "dec_next_token: margins f32 like tokens")
+    x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
+    if key_start is None:
+        args = (ws_val.data_ptr(), ws_idx.data_ptr(), ws_val.shape[1], pos.data_ptr(), prompt.data_ptr(), P, tok_cur.data_ptr(),
+                tokens.data_ptr(), tokens.shape[1], plan.ptr(margins), emb.data_ptr(), pos_tab.data_ptr(), x.data_ptr(), d, V,
+                ticket.data_ptr(), B, None)
+        plan.call(lib().pm_dec_next_token, args, _stream())
+    else:
+        _key_start(key_start, B, "dec_next_token")
+        plan.call(lib().pm_dec_next_token_ragged, plan.ragged_next_token_args(ws_val, ws_idx, pos, prompt, tok_cur, tokens, margins, emb,
+                                                                             pos_tab, key_start, x, ticket), _stream())
+    return x
+
+
+def dec_sample_topk(logits: Tensor, k: int, seed: int, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor, emb: Tensor,
+                    pos_tab: Tensor, ticket: Tensor, *, key_start: Tensor | None = None) -> Tensor:
+    """pm_dec_sample_topk (key_start None) or pm_dec_sample_topk_ragged on explicit state, as dec_next_token; logits (B, V) f32."""
+    _cuda(logits, pos, prompt, tok_cur, tokens, emb, pos_tab, ticket, key_start)
+    _tail_state("dec_sample_topk", pos, prompt, tok_cur, tokens, emb, pos_tab, ticket)
+    B, P = prompt.shape
+    V, d = emb.shape
+    _need(logits.dtype == torch.float32 and logits.shape == (B, V) and logits.stride(1) == 1 and 1 <= k <= min(64, V),
+          "dec_sample_topk: logits f32 (B, V), 1 <= k <= 64")
+    x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
+    if key_start is None:
+        args = (logits.data_ptr(), logits.stride(0), V, k, int(seed) & (2**64 - 1), pos.data_ptr(), prompt.data_ptr(), P, tok_cur.data_ptr(),
+                tokens.data_ptr(), tokens.shape[1], emb.data_ptr(), pos_tab.data_ptr(), x.data_ptr(), d, ticket.data_ptr(), B, None)
+        plan.call(lib().pm_dec_sample_topk, args, _stream())
+    else:
+        _key_start(key_start, B, "dec_sample_topk")
+        plan.call(lib().pm_dec_sample_topk_ragged, plan.ragged_sample_topk_args(logits, k, seed, pos, prompt, tok_cur, tokens, emb, pos_tab,
+                                                                               key_start, x, ticket), _stream())
+    return x
+
+
 def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eot: int, timestamp_begin: int, no_timestamps: int = -1,
                       max_initial_timestamp: int = -1, suppress=(), blank=()) -> Tensor:
     """pm_dec_whisper_rules as a standalone op (the generator puts it into its launch list): filters logits (B, V) f32 IN PLACE for

@@ -45,12 +45,54 @@ class WhisperRules:
     blank: tuple = ()
 
 
+def check_ragged(what: str, lengths, *, beams: int = 1, path: str = "auto", kv32: bool = False, fp32: bool = False) -> None:
+    """the refusals of a ragged prompt batch (``lengths`` given), before anything touches a device: each names the form that runs"""
+    if lengths is None:
+        return
+    if beams != 1:
+        raise NotImplementedError(f"{what}: lengths= (ragged prompts) follows one hypothesis per row; beam search takes a rectangular "
+                                  "prompt: beams=1, or one call per distinct prompt length without lengths=")
+    if path == "persistent":
+        raise NotImplementedError(f"{what}: lengths= does not run on path='persistent' (its self-attention stage has no per-row first "
+                                  "key); use path='launches'")
+    if kv32:
+        raise NotImplementedError(f"{what}: lengths= runs the unfused self-attention block on bf16 caches; the fp32-cache step "
+                                  "(kv32=True / exact=True) is the fused block's: one call per distinct prompt length without lengths=")
+    if fp32:
+        raise NotImplementedError(f"{what}: lengths= needs bf16 parameters (model.to(torch.bfloat16)); fp32 parameters decode through "
+                                  "greedy_exact: one call per distinct prompt length without lengths=")
+
+
+def _ragged_lengths(prompt: Tensor, lengths, longest: int | None = None) -> Tensor:
+    """``lengths`` of a right-padded (B, P) prompt as int64 (B,) on the host; ValueError unless 1 <= len_b <= P (<= longest)"""
+    if prompt.dim() != 2 or prompt.dtype != torch.int64 or prompt.shape[1] < 1:
+        raise ValueError("greedy decode: prompt must be int64 (B, P >= 1)")
+    B, P = prompt.shape
+    lens = lengths.detach().cpu() if isinstance(lengths, Tensor) else torch.as_tensor(list(lengths))
+    if lens.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or lens.shape != (B,):
+        raise ValueError(f"greedy decode: lengths must be a sequence or integer tensor of shape ({B},), one prompt length per row")
+    lens = lens.to(torch.int64)
+    if B and (int(lens.min()) < 1 or int(lens.max()) > P):
+        raise ValueError(f"greedy decode: every length must be in 1..{P} (the prompt's width)")
+    if longest is not None and B and int(lens.max()) > longest:
+        raise ValueError(f"greedy decode: this decoder was built for prompts of up to {longest} tokens")
+    return lens
+
+
+def _right_align(prompt: Tensor, lens: Tensor, width: int, pad: int) -> Tensor:
+    """(B, width) with row b's len_b tokens at columns width - len_b .. width - 1 and ``pad`` in front (host indexing, no kernel)"""
+    idx = torch.arange(width)[None, :] - (width - lens)[:, None]
+    dev = prompt.device
+    return torch.where((idx >= 0).to(dev), prompt.gather(1, idx.clamp(min=0).to(dev)), torch.full((), pad, dtype=torch.int64, device=dev))
+
+
 class GreedyDecoder(plan.CapturedStep):
     """State + launch list of the decode step for one (decoder, batch, memory length) geometry."""
 
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
                  topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
-                 beams: int = 1, eos: int | None = None, prefill: bool = False, prefill_chunk: int | None = None) -> None:
+                 beams: int = 1, eos: int | None = None, prefill: bool = False, prefill_chunk: int | None = None, lengths=None,
+                 pad_token_id: int = 0) -> None:
         """``kv32``: the reference-accuracy form of the same step - fp32 memory in, cross and self K/V kept in fp32 (nothing is
         rounded when it is cached; pm_dec_attention_fused_kv32), everything else as in the throughput path, whose projections
         are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it.
@@ -58,10 +100,17 @@ class GreedyDecoder(plan.CapturedStep):
         the beam kernels instead of a token choice; ``beams`` = 1 builds exactly the launch list it always did.
         ``prefill``: prompt positions 0 .. P - 2 go through the layers as one batched pass per ``prefill_chunk`` positions
         (default 512, PM_PREFILL_CHUNK) that fills the self-attention caches (prefill()); the step then starts at position
-        P - 1 and runs n_new times instead of P + n_new - 1.  The step itself, and everything after the caches, is unchanged."""
+        P - 1 and runs n_new times instead of P + n_new - 1.  The step itself, and everything after the caches, is unchanged.
+        ``lengths`` (B,) with 1 <= len_b <= P: a RAGGED batch - ``prompt`` is right-padded, row b's prompt is prompt[b, :len_b]
+        (DESIGN.md section 19).  Internally the rows are right-aligned to Pm = max(lengths): row b's tokens sit at cache positions
+        key_start[b] = Pm - len_b .. Pm - 1, ``P`` / ``Ttot`` / ``tokens`` / ``margins`` are in that layout (Pm + n_new wide), and
+        output() shifts back.  The step keeps its one device position; the self block runs unfused (pm_dec_linear mode 1 +
+        pm_dec_attention_ragged), the embedding rows take pos[max(0, t - key_start[b])].  Any ``lengths`` - all equal to P too -
+        takes this path; ``lengths=None`` builds exactly the launch list it always did."""
         if path not in ("auto", "launches", "persistent"):
             raise ValueError("greedy decode: path must be 'auto', 'launches' or 'persistent'")
         self.W = int(beams)
+        prompt, path = self._check_ragged(dec, prompt, lengths, pad_token_id, n_new, path, kv32)
         path = self._check_prefill(dec, prefill, prefill_chunk, path, kv32)
         path = self._check_request(path, topk, margins)
         prompt = self._check_geometry(dec, memory, prompt, n_new, kv32)
@@ -108,6 +157,26 @@ class GreedyDecoder(plan.CapturedStep):
             raise NotImplementedError("greedy decode: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 parameters "
                                       "decode through greedy_exact, token by token: prefill=False")
         return "launches"  # 'auto' never picks the persistent kernel under prefill
+
+    def _check_ragged(self, dec, prompt: Tensor, lengths, pad: int, n_new: int, path: str, kv32: bool) -> tuple:
+        """the refusals and the argument checks of a ragged batch; returns (the right-aligned (B, max(lengths)) prompt, path).
+        Sets _ragged, _P_in (the caller's prompt width), _pad and _starts (host int64 (B,): each row's first cache position)."""
+        self._ragged, self._pad, self._starts = lengths is not None, int(pad), None
+        self._P_in = prompt.shape[1] if prompt.dim() == 2 else 0
+        if lengths is None:
+            return prompt, path
+        E = dec.token_embs.weight
+        check_ragged("greedy decode", lengths, beams=self.W, path=path, kv32=kv32, fp32=E.dtype == torch.float32)
+        lens = _ragged_lengths(prompt, lengths)
+        longest = int(lens.max())
+        if longest + n_new > dec.pos_embs.shape[0]:
+            raise ValueError(f"greedy decode: {longest + n_new} positions (max(lengths) + new tokens) > max_seq_len {dec.pos_embs.shape[0]}")
+        if not 0 <= self._pad < E.shape[0]:
+            raise ValueError("greedy decode: pad_token_id outside the vocabulary")
+        if int(prompt.min()) < 0 or int(prompt.max()) >= E.shape[0]:  # the padding too: its ids go through the embedding
+            raise ValueError("greedy decode: prompt ids out of range")
+        self._starts = longest - lens
+        return _right_align(prompt, lens, longest, self._pad), "launches"  # 'auto' never picks the persistent kernel for a ragged batch
 
     def _check_request(self, path: str, topk: int, margins: bool) -> str:
         if self.W != 1:
@@ -197,6 +266,8 @@ class GreedyDecoder(plan.CapturedStep):
         # launch and one ticket pass per layer less.  Needs both blocks fused (their workgroups own whole rows).
         self._chain = (self._fuse_self and self._fuse_cross and memory is not None and self.path != "persistent" and not v2
                        and os.environ.get("PM_DEC_CHAIN", "1") != "0")
+        if self._ragged:  # the fused self block and the chain have no per-row first key: the unfused pair; the cross block stays
+            self._fuse_self = self._chain = False
 
     def _allocate(self, dec, memory, prompt: Tensor, margins: bool) -> None:
         """the state of a run and the scratch rows of a step"""
@@ -226,6 +297,10 @@ class GreedyDecoder(plan.CapturedStep):
         # x for position 0 comes from reset(); every later x row is written by the previous step's pm_dec_next_token
         self._embed0 = (L.pm_dec_embed, (self.tok_cur.data_ptr(), E.data_ptr(), self._pos_tab.data_ptr(), self.pos.data_ptr(),
                                          self.x.data_ptr(), B, d, V, None))
+        self.key_start = None
+        if self._ragged:  # in device memory: the captured step serves any lengths, rebind() rewrites it in place
+            self.key_start = self._starts.to(device=dev, dtype=torch.int32)
+            self._embed0 = (L.pm_dec_embed_ragged, plan.ragged_embed_args(self.tok_cur, E, self._pos_tab, self.pos, self.key_start, self.x))
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.fc2_parts = None
         self.head_parts = torch.empty(B * self.H * d, **f32) if self._chain else None
@@ -262,7 +337,11 @@ class GreedyDecoder(plan.CapturedStep):
                                                         n_keys=Tmax))
         else:
             self.linear(cur, wqkv, self.q, ln=ln, bias=bqkv, mode=1, cache=(kc, vc))
-            self.add(L.pm_dec_attention, *plan.attention_args(self.q, kv, self.att, B, H, pos=self.pos, lk_add=1, lk_max=Tmax))
+            if self._ragged:
+                self.add(L.pm_dec_attention_ragged, *plan.ragged_attention_args(self.q, kv, self.att, B, H, pos=self.pos, lk_add=1,
+                                                                                lk_max=Tmax, key_start=self.key_start))
+            else:
+                self.add(L.pm_dec_attention, *plan.attention_args(self.q, kv, self.att, B, H, pos=self.pos, lk_add=1, lk_max=Tmax))
         if self.path != "persistent" and not self._chain:
             self.linear(self.att, wo, cur, bias=bo, resid=cur)
 
@@ -377,6 +456,10 @@ class GreedyDecoder(plan.CapturedStep):
         if topk == 1 and rules is None:
             self.linear(xl, E, None, ln=ln, mode=2)
             # token choice + the next step's embedding row + position advance: one launch
+            if self._ragged:
+                return self.add(L.pm_dec_next_token_ragged, *plan.ragged_next_token_args(
+                    self.ws_val, self.ws_idx, self.pos, self.prompt, self.tok_cur, self.tokens, self.margins, E, self._pos_tab,
+                    self.key_start, self.x, self.ticket))
             self.add(L.pm_dec_next_token, self.ws_val.data_ptr(), self.ws_idx.data_ptr(), self._n_tiles, self.pos.data_ptr(),
                      self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot, plan.ptr(self.margins),
                      E.data_ptr(), self._pos_tab.data_ptr(), self.x.data_ptr(), d, V, self.ticket.data_ptr(), B, None)
@@ -384,6 +467,10 @@ class GreedyDecoder(plan.CapturedStep):
             if margins:
                 raise ValueError("greedy decode: margins are an arg-max diagnostic (topk == 1)")
             self._full_logits(xl, ln, rules)
+            if self._ragged:
+                return self.add(L.pm_dec_sample_topk_ragged, *plan.ragged_sample_topk_args(
+                    self.logits, topk, seed, self.pos, self.prompt, self.tok_cur, self.tokens, E, self._pos_tab, self.key_start, self.x,
+                    self.ticket))
             self.add(L.pm_dec_sample_topk, self.logits.data_ptr(), self.logits.stride(0), V, topk, int(seed) & (2**64 - 1),
                      self.pos.data_ptr(), self.prompt.data_ptr(), P, self.tok_cur.data_ptr(), self.tokens.data_ptr(), self.Ttot,
                      E.data_ptr(), self._pos_tab.data_ptr(), self.x.data_ptr(), d, self.ticket.data_ptr(), B, None)
@@ -442,7 +529,10 @@ class GreedyDecoder(plan.CapturedStep):
         tok.copy_(self.prompt[:, p0 : p0 + c])
         x, y = view(self._pre_x[0], d), view(self._pre_x[1], d)
         xn, qkv, att, q = view(self._pre_xn, d), view(self._pre_qkv, 3 * inner), view(self._pre_att, inner), view(self._pre_qkv, inner)
-        ops.embed_tokens(tok, self._E, self._pos_tab, pos0=p0, out_dtype=torch.float32, out=x.view(B, c, d))
+        if self._ragged:
+            ops.embed_tokens_ragged(tok, self._E, self._pos_tab, self.key_start, pos0=p0, out_dtype=torch.float32, out=x.view(B, c, d))
+        else:
+            ops.embed_tokens(tok, self._E, self._pos_tab, pos0=p0, out_dtype=torch.float32, out=x.view(B, c, d))
         for l, rec in enumerate(self._pre_layers):
             if log is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -450,7 +540,10 @@ class GreedyDecoder(plan.CapturedStep):
                 log.append((l, e0, e1))
             ops.layernorm(x, *rec["sa_ln"], out=xn)
             ops.linear(xn, *rec["wqkv"], out=qkv)
-            ops.prefill_attention(qkv, self.self_k[l], self.self_v[l], H, p0, out=att)
+            if self._ragged:
+                ops.prefill_attention_ragged(qkv, self.self_k[l], self.self_v[l], H, p0, self.key_start, out=att)
+            else:
+                ops.prefill_attention(qkv, self.self_k[l], self.self_v[l], H, p0, out=att)
             if l + 1 < len(self._pre_layers):
                 ops.linear(att, *rec["so"], resid=x, out=y)
                 x, y = y, x
@@ -480,10 +573,20 @@ class GreedyDecoder(plan.CapturedStep):
         self.tok_cur.copy_(self.prompt[:, self.P - 1])
         self.start()  # x[b] = emb[prompt[b, P - 1]] + pos[P - 1]
 
-    def rebind(self, memory: Tensor, prompt: Tensor) -> None:
+    def rebind(self, memory: Tensor, prompt: Tensor, lengths=None) -> None:
         """New clips, same geometry: re-project the cross K/V INTO the existing buffers and swap the prompt, so the
-        captured graph (which holds raw pointers) stays valid."""
-        assert (self.clips, self.P) == tuple(prompt.shape)
+        captured graph (which holds raw pointers) stays valid.  A decoder built with ``lengths`` takes new ones here (each at
+        most the longest it was built for): key_start is rewritten in place, the same graph serves them."""
+        assert (self.clips, self._P_in) == tuple(prompt.shape)
+        if self._ragged != (lengths is not None):
+            raise ValueError("greedy decode: rebind() takes lengths= exactly when the decoder was built with lengths=")
+        if self._ragged:
+            lens = _ragged_lengths(prompt, lengths, longest=self.P)
+            if int(prompt.min()) < 0 or int(prompt.max()) >= self.V:
+                raise ValueError("greedy decode: prompt ids out of range")
+            self._starts = self.P - lens
+            self.key_start.copy_(self._starts.to(torch.int32))
+            prompt = _right_align(prompt, lens, self.P, self._pad)
         if memory is not None:
             B, S, d = memory.shape
             assert B == self.clips and memory.dtype == (torch.float32 if self.kv32 else torch.bfloat16)
@@ -510,6 +613,19 @@ class GreedyDecoder(plan.CapturedStep):
         for _ in range(self.n_steps):
             one_step()
         return self.tokens
+
+    def output(self) -> tuple:
+        """(tokens, margins or None) of the last run in the caller's layout.  Rectangular prompts: the state itself.  Ragged: (B,
+        P + n_new), row b = its prompt, its new ids, then P - len_b times pad_token_id (margins: zeros) - host indexing of the
+        right-aligned state."""
+        if not self._ragged:
+            return self.tokens, self.margins
+        dev = self.tokens.device
+        idx = torch.arange(self._P_in + self.Ttot - self.P)[None, :] + self._starts[:, None]
+        live, idx = (idx < self.Ttot).to(dev), idx.clamp(max=self.Ttot - 1).to(dev)
+        toks = torch.where(live, self.tokens.gather(1, idx), torch.full((), self._pad, dtype=torch.int64, device=dev))
+        marg = None if self.margins is None else torch.where(live, self.margins.gather(1, idx), torch.zeros((), device=dev))
+        return toks, marg
 
     def check(self) -> None:
         """Raise if a hand-off inside the persistent step kernel gave up (one read-back: call it where the tokens are consumed)."""
@@ -623,19 +739,25 @@ def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams
 @torch.no_grad()
 def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: bool = True, margins: bool = False,
                   fused: bool = True, topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto",
-                  kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None):
+                  kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None, lengths=None, pad_token_id: int = 0):
     """tokens (B, P + n_new) int64 [and per-position diagnostic margins].  fused=False uses the unfused
     projection + attention launches (same arithmetic, 2 more launches per layer); topk > 1 samples each token from the
     softmax over the k largest logits on the device (same seed -> same ids); path: "persistent" (all layers of a step in
     one launch), "launches" (a launch per stage) or "auto".  ``prefill``: the prompt's positions 0 .. P - 2 fill the caches in
     one batched pass per ``prefill_chunk`` positions (default 512) instead of one decode step each, and the step runs n_new
     times; bf16 parameters and caches, not path="persistent" (NotImplementedError otherwise).  The prompt pass rounds where
-    forward() does, so its ids follow forward()'s contract (rel-L2 2e-2 on the logits), not the step's fp32-exact projections."""
+    forward() does, so its ids follow forward()'s contract (rel-L2 2e-2 on the logits), not the step's fp32-exact projections.
+    ``lengths`` (a sequence or integer tensor (B,), 1 <= len_b <= P): a ragged batch - ``prompt`` is right-padded, row b of the result
+    is prompt[b, :len_b], its n_new new ids, then P - len_b times ``pad_token_id``; margins are aligned the same way.  Row b is what
+    this function returns for prompt[b:b+1, :len_b] alone.  Works with prefill, rules and top-k sampling (the draw is keyed by
+    (seed, cache position, row), so a row's draws differ from those of the same row decoded alone); not with beams, path="persistent",
+    kv32 or fp32 parameters (NotImplementedError), ValueError for lengths outside 1..P or max(lengths) + n_new > max_seq_len."""
     st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32, prefill=prefill,
-                       prefill_chunk=prefill_chunk)
-    toks = st.run(graph)
+                       prefill_chunk=prefill_chunk, lengths=lengths, pad_token_id=pad_token_id)
+    st.run(graph)
     st.check()
-    return (toks, st.margins) if margins else toks
+    toks, marg = st.output()
+    return (toks, marg) if margins else toks
 
 
 @torch.no_grad()

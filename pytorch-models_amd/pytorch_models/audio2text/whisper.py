@@ -118,15 +118,20 @@ class WhisperDecoder(nn.Module):
     @torch.no_grad()
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
         """Batched greedy decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids.  ``rules``: a
         generate.WhisperRules (token suppression, timestamp pairing / monotonicity) applied to the logits on the device;
         ``path``: "persistent" / "launches" / "auto" (generate.GreedyDecoder).  ``beams`` > 1: beam search of that width
         (generate.beam_decode; 1..8, B * beams <= 64) - the best hypothesis, or with ``return_beams`` (tokens (B, beams, P + n),
         scores (B, beams)), best first; ``eos_token_id`` ends a hypothesis (default: rules.eot under rules).  ``prefill``: the
-        prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode; bf16 model and memory)."""
-        from .generate import beam_decode, greedy_decode, greedy_exact
+        prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode; bf16 model and memory).
+        ``lengths`` (B,), 1 <= len_b <= P: a ragged batch - ``prompt`` is right-padded, row b of the result is prompt[b, :len_b], its
+        new ids, then P - len_b times ``pad_token_id``: what generate() returns for that clip and prompt alone (generate.greedy_decode;
+        bf16 model and memory, beams = 1, not path="persistent")."""
+        from .generate import beam_decode, check_ragged, greedy_decode, greedy_exact
 
+        check_ragged("WhisperDecoder.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
+                     kv32=memory is not None and memory.dtype == torch.float32, fp32=self.token_embs.weight.dtype == torch.float32)
         if prefill and self.token_embs.weight.dtype == torch.float32:
             raise NotImplementedError("WhisperDecoder.generate: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 "
                                       "parameters decode through greedy_exact, token by token: prefill=False")
@@ -140,7 +145,8 @@ class WhisperDecoder(nn.Module):
             if rules is not None:
                 raise NotImplementedError("WhisperDecoder.generate: the decoding rules run on the bf16 model's step kernels")
             return greedy_exact(self, memory, prompt, max_new_tokens)
-        return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill)
+        return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
+                             lengths=lengths, pad_token_id=pad_token_id)
 
 
 class Whisper(nn.Module):
@@ -159,13 +165,18 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",
                  exact: bool = False, beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
         """log-mel (B, n_mels, T) + prompt ids (B, P) -> greedy ids (B, P + max_new_tokens); ``beams`` > 1: beam search
         (WhisperDecoder.generate), with ``exact=True`` on the fp32-cache step (B * beams * n_heads <= 256).
         ``exact=True`` (bf16 model): the whole pipeline - encoder, cross K/V, decoder, caches - in fp32 on an fp32 copy of
         this model's (bf16-valued) weights: the ids are those of the reference's fp32 forward on the same weights, bit for
         bit (tests/test_hip_exact.py); costs ~10x the bf16 encoder and an eager fp32 step loop.  A model whose
-        parameters are fp32 always decodes this way.  ``prefill``: WhisperDecoder.generate's; not with ``exact``."""
+        parameters are fp32 always decodes this way.  ``prefill``: WhisperDecoder.generate's; not with ``exact``.
+        ``lengths`` / ``pad_token_id``: WhisperDecoder.generate's ragged prompt batch; not with ``exact``, beams or fp32 parameters."""
+        from .generate import check_ragged
+
+        check_ragged("Whisper.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
+                     fp32=self.decoder.token_embs.weight.dtype == torch.float32)
         if prefill and exact:
             raise NotImplementedError("Whisper.generate: prefill=True fills bf16 caches; exact=True promises bit equality with the "
                                       "reference and keeps the token-by-token prompt: prefill=False")
@@ -188,7 +199,8 @@ class Whisper(nn.Module):
             if rules is None and prompt.shape[0] * H <= 256 and prompt.shape[0] <= 64:
                 return greedy_decode(self.decoder, twin.encoder(x), prompt, max_new_tokens, graph=graph, kv32=True)
             return twin.generate(x, prompt, max_new_tokens)
-        return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill)
+        return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
+                                     lengths=lengths, pad_token_id=pad_token_id)
 
     def exact_copy(self) -> "Whisper":
         """fp32 twin of this model (same values: bf16 -> fp32 is exact), rebuilt when a parameter changes."""

@@ -74,6 +74,45 @@ class DecoderGenerator:
                 break
         return tokens
 
+    @torch.inference_mode()
+    def generate_ids_batch(self, prompts: list[list[int]], max_tokens: int = 100, topk: int = 1, eos_token_id: int | None = None,
+                           seed: int = 0, prefill: bool = False) -> list[list[int]]:
+        """generate_ids() for a batch of prompts of different lengths: one ragged call of the model's KV-cached generate() per shard
+        of at most 64 prompts (right-padded, ``lengths=``), the padding stripped, each row cut after its first eos_token_id (kept).
+        Greedy rows are what generate_ids() returns for them; top-k draws are keyed by (seed, cache position, row) and differ from
+        the row's own run.  A shard decodes min(max_tokens, room of its LONGEST prompt) new tokens per row.  A model without the
+        KV-cached step (post-norm GPT, fp32 parameters) goes through generate_ids() row by row."""
+        prompts = [list(p) for p in prompts]
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError("DecoderGenerator: every prompt needs at least one token")
+        p0 = next(self.model.parameters())
+        kv_ok = p0.dtype == torch.bfloat16 and all(l.pre_norm for l in self.model.layers)
+        if not (topk <= 64 and hasattr(self.model, "generate") and kv_ok):
+            return [self.generate_ids(p, max_tokens, topk, eos_token_id, seed=seed, prefill=prefill) for p in prompts]
+        out = []
+        for s in range(0, len(prompts), 64):
+            shard = prompts[s : s + 64]
+            lens = [len(p) for p in shard]
+            width = max(lens)
+            n_new = min(max_tokens, self.model.pos_embs.shape[0] - width) if hasattr(self.model, "pos_embs") else max_tokens
+            padded = torch.zeros(len(shard), width, dtype=torch.int64)
+            for row, p in zip(padded, shard):
+                row[: len(p)] = torch.tensor(p)
+            toks = self.model.generate(padded.to(p0.device), n_new, topk=topk, seed=seed, lengths=lens, pad_token_id=0,
+                                       **({"prefill": True} if prefill else {})).tolist()
+            for p, row in zip(shard, toks):
+                new = row[len(p) : len(p) + n_new]
+                if eos_token_id is not None and eos_token_id in new:
+                    new = new[: new.index(eos_token_id) + 1]
+                out.append(p + new)
+        return out
+
+    def generate_batch(self, prompts: list[str], max_tokens: int = 100, topk: int = 1, prefill: bool = False) -> list[str]:
+        """generate() for a batch of prompts: one ragged batched decode (generate_ids_batch)"""
+        ids = self.generate_ids_batch([self.tokenizer.encode(p) for p in prompts], max_tokens, topk,
+                                      getattr(self.tokenizer, "eos_token_id", None), prefill=prefill)
+        return [self.tokenizer.decode(i) for i in ids]
+
     def generate(self, prompt: str, max_tokens: int = 100, topk: int = 1, prefill: bool = False) -> str:
         ids = self.generate_ids(self.tokenizer.encode(prompt), max_tokens, topk, getattr(self.tokenizer, "eos_token_id", None),
                                 prefill=prefill)

@@ -51,13 +51,18 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, topk: int = 1, seed: int = 0,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
         """Batched decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids; greedy (topk = 1) or
         top-k sampling on the device (softmax over the k largest logits; the same seed gives the same ids); ``beams`` > 1:
         beam search (audio2text.generate.beam_decode), with ``return_beams`` (tokens (B, beams, P + n), scores (B, beams)).
-        ``prefill``: the prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode)."""
-        from ..audio2text.generate import beam_decode, greedy_decode, greedy_exact
+        ``prefill``: the prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode).
+        ``lengths`` (B,), 1 <= len_b <= P: a ragged batch - ``prompt`` is right-padded, row b of the result is prompt[b, :len_b], its
+        new ids, then P - len_b times ``pad_token_id``: what generate() returns for that row alone (greedy; top-k draws are keyed
+        by the cache position, so they differ from the row's own run).  bf16 parameters, beams = 1, not path="persistent"."""
+        from ..audio2text.generate import beam_decode, check_ragged, greedy_decode, greedy_exact
 
+        check_ragged("GPT2.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
+                     fp32=self.token_embs.weight.dtype == torch.float32)
         if prefill and self.token_embs.weight.dtype == torch.float32:
             raise NotImplementedError("GPT2.generate: prefill=True needs bf16 parameters (model.to(torch.bfloat16)); fp32 parameters "
                                       "decode through greedy_exact, token by token: prefill=False")
@@ -70,7 +75,8 @@ class GPT2(nn.Module):
                                return_beams=return_beams, prefill=prefill)
         if self.token_embs.weight.dtype == torch.float32 and topk == 1:  # fp32 parameters: fp32 end to end
             return greedy_exact(self, None, prompt, max_new_tokens)
-        return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path, prefill=prefill)
+        return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path, prefill=prefill,
+                             lengths=lengths, pad_token_id=pad_token_id)
 
     @staticmethod
     def from_hf(model_tag: str, *, pretrained=False, **kwargs) -> "GPT2":
