@@ -74,6 +74,17 @@ int pm_linear_bf16_ws(const void* x, int64_t ldx, int64_t x_rows_per_batch, int6
                       const float* ln_s, float* ln_row_out, void* ws, int64_t ws_bytes, void* stream);
 int64_t pm_linear_ws_bytes(void);
 
+/* Host-only query: the kernel a pm_linear_bf16_ws call with these arguments would launch.  1 = 128 x 128, 2 = persistent
+ * 256 x 128, 3 = 256 x 256, 4 / 5 = the stream-K / hybrid experiments, 6 / 7 = (64 MI) x 256 tiles of 256 / 320 rows; 0 when
+ * M == 0 (nothing is launched); minus the error code the call would return.  The launch takes its decision from the same
+ * function.  Pointers are looked at for null and alignment only: nothing is dereferenced or launched, no GPU is needed.
+ * PM_GEMM_KERNEL (read once per process) forces a kernel where it applies and silently falls through where it does not -
+ * this query is how a test learns which one ran. */
+int pm_linear_bf16_plan(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w,
+                        int64_t ldw, const float* bias, const void* resid, int64_t ldr, int resid_dtype, int64_t resid_period,
+                        const void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act,
+                        const float* ln_stats, const float* ln_s, const float* ln_row_out, const void* ws, int64_t ws_bytes);
+
 /* LayerNorm folded into the GEMMs around it (pre-norm blocks, transformer.py:124-125: x + f(LN(x))).
  * pm_linear_bf16_ln = pm_linear_bf16_ex plus
  *  - ln_stats (M, 2) f32 [mean, rstd per input row] and ln_s (N) f32: y = act(rstd*(x w'^T - mean*ln_s) + bias) + resid,

@@ -113,9 +113,13 @@ __device__ __forceinline__ float erf_fast(float x) {
 }
 
 // erf-GELU without transcendentals for bf16 outputs: Phi(x) - 1/2 = x q(x^2) with q a degree-8 minimax polynomial
-// on |x| <= 4.5 (x clamped beyond: Phi(4.5) = 1 - 3.4e-6).  |gelu_poly(x) - x Phi(x)| <= 3.7e-5 for all x, i.e.
-// >= 100x below the bf16 rounding of the result wherever |result| > 1e-2.  11 VALU ops, all packable; the erf_fast
-// form costs ~16 including an exp and an rcp at quarter rate - the fc1 epilogue is VALU-bound, so this matters.
+// on |x| <= 4.5 (x clamped beyond: Phi(4.5) = 1 - 3.4e-6).  |gelu_poly(x) - x Phi(x)| <= 3.7e-5 for all finite x, i.e.
+// >= 100x below the bf16 rounding of the result wherever |result| > 1e-2.  The factor 1/2 + xc q is kept in [0, 1] (the
+// clamp output modifier of its v_fma_f32: no instruction of its own): the polynomial leaves it at -4.0e-6 at xc = -4.5 (Phi(-4.5) = +3.4e-6) and at 1 + 4.0e-6 at +4.5, which
+// times the UNCLAMPED x grew as 4.0e-6 |x| on both sides (+0.26 at x = -65000, positive where erf-GELU is -0).  Kept in
+// range, x <= -4.5 gives -0 and x >= 4.5 gives x, as erf-GELU does in fp32 (|x Phi(x)| and x - x Phi(x) <= 1.6e-5 there).
+// 11 VALU ops, all but the clamp of x and the last fma packable; the erf_fast form costs ~16 including an exp and an rcp at quarter
+// rate - the fc1 epilogue is VALU-bound, so this matters.
 __device__ __forceinline__ float gelu_poly(float x) {
   const float xc = __builtin_amdgcn_fmed3f(x, -4.5f, 4.5f);
   const float t = fmaf(xc * xc, 2.0f / 20.25f, -1.0f);
@@ -128,16 +132,16 @@ __device__ __forceinline__ float gelu_poly(float x) {
   q = fmaf(q, t, 5.481856801e-02f);
   q = fmaf(q, t, -7.717196008e-02f);
   q = fmaf(q, t, 1.569021127e-01f);
-  return x * fmaf(xc, q, 0.5f);
+  return x * __builtin_amdgcn_fmed3f(fmaf(xc, q, 0.5f), 0.0f, 1.0f);
 }
 
 // The same polynomial on two values at once: v_pk_mul_f32 / v_pk_fma_f32 halve the instruction count of the fc1
-// epilogue's activation (only the clamp has no packed form).  Bit-identical to gelu_poly per element.
+// epilogue's activation (only the clamp of x and the last, clamping fma have no packed form).  Bit-identical to gelu_poly per element.
 __device__ __forceinline__ f32x2 gelu_poly2(f32x2 x) {
   f32x2 xc;
   xc[0] = __builtin_amdgcn_fmed3f(x[0], -4.5f, 4.5f);
   xc[1] = __builtin_amdgcn_fmed3f(x[1], -4.5f, 4.5f);
-  const f32x2 k1 = {2.0f / 20.25f, 2.0f / 20.25f}, m1 = {-1.0f, -1.0f}, half = {0.5f, 0.5f};
+  const f32x2 k1 = {2.0f / 20.25f, 2.0f / 20.25f}, m1 = {-1.0f, -1.0f};
   const f32x2 t = __builtin_elementwise_fma(xc * xc, k1, m1);
   f32x2 q = {3.353692146e-03f, 3.353692146e-03f};
   q = __builtin_elementwise_fma(q, t, f32x2{-9.328538250e-03f, -9.328538250e-03f});
@@ -148,7 +152,12 @@ __device__ __forceinline__ f32x2 gelu_poly2(f32x2 x) {
   q = __builtin_elementwise_fma(q, t, f32x2{5.481856801e-02f, 5.481856801e-02f});
   q = __builtin_elementwise_fma(q, t, f32x2{-7.717196008e-02f, -7.717196008e-02f});
   q = __builtin_elementwise_fma(q, t, f32x2{1.569021127e-01f, 1.569021127e-01f});
-  return x * __builtin_elementwise_fma(xc, q, half);
+  // the last fma per element: v_fma_f32 carries the [0, 1] clamp as its output modifier (no instruction of its own), the packed
+  // form does not - one v_pk_fma_f32 plus two clamps would be three instructions instead of these two
+  f32x2 f;
+  f[0] = __builtin_amdgcn_fmed3f(fmaf(xc[0], q[0], 0.5f), 0.0f, 1.0f);
+  f[1] = __builtin_amdgcn_fmed3f(fmaf(xc[1], q[1], 0.5f), 0.0f, 1.0f);
+  return x * f;
 }
 
 // activation of four values (the GEMM epilogues' unit): packed for GELU, element-wise otherwise

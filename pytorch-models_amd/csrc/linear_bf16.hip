@@ -584,26 +584,29 @@ static int pm_linear_pick_kernel(int64_t M, int64_t N, int64_t K, bool persist_o
   return cp <= cs ? PM_K_PERSIST : PM_K_SMALL;
 }
 
-static int linear_impl(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w,
-                       int64_t ldw, const float* bias, const void* resid, int64_t ldr, int resid_dtype,
-                       int64_t resid_period, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act,
-                       PmLnFold ln, void* stream, void* ws = nullptr, int64_t ws_bytes = 0) {
-  if (!x || !w || !y || M < 0 || N <= 0 || K <= 0) return PM_EINVAL;
+// THE decision site: argument checks and kernel choice of one pm_linear_bf16* call, host arithmetic only (pointers are looked at
+// for null and alignment, never dereferenced).  Returns the kernel id (PM_K_*), 0 when M == 0 (nothing to launch), or minus the
+// error code.  linear_impl launches what this returns and pm_linear_bf16_plan reports it, so the two cannot drift apart.
+static int linear_decide(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w,
+                         int64_t ldw, const float* bias, const void* resid, int64_t ldr, int resid_dtype,
+                         int64_t resid_period, const void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act,
+                         PmLnFold ln, const void* ws, int64_t ws_bytes, int* vec_ok_out) {
+  if (!x || !w || !y || M < 0 || N <= 0 || K <= 0) return -PM_EINVAL;
   const bool want_ln = ln.stats || ln.row_out;
-  if ((ln.stats == nullptr) != (ln.s == nullptr)) return PM_EINVAL;
-  if (ln.row_out && N % 64) return PM_EUNSUPPORTED;
-  if (M == 0) return PM_OK;
-  if (y_dtype != PM_BF16 && y_dtype != PM_F32) return PM_EINVAL;
-  if (resid && resid_dtype != PM_BF16 && resid_dtype != PM_F32) return PM_EINVAL;
-  if (K % 8 != 0) return PM_EUNSUPPORTED;  // 16-byte chunks; a K tail below 64 is zero-filled by the 128 x 128 kernel
-  if (ldx < 0 || ldw < K || ldy < N || (resid && ldr < N) || x_rows_per_batch < 0 || resid_period < 0) return PM_EINVAL;
-  if (ldx % 8 || ldw % 8 || x_batch_stride % 8) return PM_EALIGN;
-  if (((uintptr_t)x | (uintptr_t)w) & 15) return PM_EALIGN;
+  if ((ln.stats == nullptr) != (ln.s == nullptr)) return -PM_EINVAL;
+  if (ln.row_out && N % 64) return -PM_EUNSUPPORTED;
+  if (M == 0) return 0;
+  if (y_dtype != PM_BF16 && y_dtype != PM_F32) return -PM_EINVAL;
+  if (resid && resid_dtype != PM_BF16 && resid_dtype != PM_F32) return -PM_EINVAL;
+  if (K % 8 != 0) return -PM_EUNSUPPORTED;  // 16-byte chunks; a K tail below 64 is zero-filled by the 128 x 128 kernel
+  if (ldx < 0 || ldw < K || ldy < N || (resid && ldr < N) || x_rows_per_batch < 0 || resid_period < 0) return -PM_EINVAL;
+  if (ldx % 8 || ldw % 8 || x_batch_stride % 8) return -PM_EALIGN;
+  if (((uintptr_t)x | (uintptr_t)w) & 15) return -PM_EALIGN;
   const int vec_ok = (N % 4 == 0) && (ldy % 4 == 0) && (!resid || ldr % 4 == 0) &&
                      !((uintptr_t)y & (y_dtype == PM_F32 ? 15 : 7)) && !(bias && ((uintptr_t)bias & 15)) &&
                      !(resid && ((uintptr_t)resid & (resid_dtype == PM_F32 ? 15 : 7)));
-  if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30) || resid_period > (1 << 30)) return PM_EINVAL;
-  hipStream_t st0 = (hipStream_t)stream;
+  if (vec_ok_out) *vec_ok_out = vec_ok;
+  if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30) || resid_period > (1 << 30)) return -PM_EINVAL;
   const bool out_vec16 = N % 8 == 0 && ldy % 8 == 0 && !((uintptr_t)y & 15);
   const bool wide_base = y_dtype == PM_BF16 && vec_ok && out_vec16 && !(resid && resid_dtype != PM_BF16) &&
                          !(resid && (ldr % 8 || ((uintptr_t)resid & 15))) &&
@@ -623,12 +626,30 @@ static int linear_impl(const void* x, int64_t ldx, int64_t x_rows_per_batch, int
                        !(ln.stats && (resid || ln.row_out)) && !(ln.row_out && act != PM_ACT_NONE);
   int kernel;
   if (want_ln) {  // the LayerNorm fold lives in the persistent kernels' epilogues (row partials: the tile and 256 x 128 kernels)
-    if (!staged_ok) return PM_EUNSUPPORTED;
+    if (!staged_ok) return -PM_EUNSUPPORTED;
     kernel = pm_linear_pick_kernel(M, N, K, true, wide_ok, sk_ok, hyb_ok, resid != nullptr, tile_ok);
     if (kernel == PM_K_SMALL) kernel = PM_K_PERSIST;
   } else {
     kernel = pm_linear_pick_kernel(M, N, K, persist_ok, wide_ok, sk_ok, hyb_ok, resid != nullptr, tile_ok);
   }
+  const bool big = kernel == PM_K_PERSIST;
+  if (kernel == PM_K_SMALL || big) {
+    const int64_t nblk = ((M + (big ? LBM : BM) - 1) / (big ? LBM : BM)) * ((N + BN - 1) / BN);
+    if (nblk > 0x7fffffff) return -PM_EINVAL;
+    if (act < PM_ACT_NONE || act > PM_ACT_SILU) return -PM_EINVAL;  // the two 128-wide kernels serve the whole table
+  }
+  return kernel;
+}
+
+static int linear_impl(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w,
+                       int64_t ldw, const float* bias, const void* resid, int64_t ldr, int resid_dtype,
+                       int64_t resid_period, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act,
+                       PmLnFold ln, void* stream, void* ws = nullptr, int64_t ws_bytes = 0) {
+  int vec_ok = 0;
+  const int kernel = linear_decide(x, ldx, x_rows_per_batch, x_batch_stride, w, ldw, bias, resid, ldr, resid_dtype, resid_period, y,
+                                   ldy, y_dtype, M, N, K, act, ln, ws, ws_bytes, &vec_ok);
+  if (kernel <= 0) return -kernel;  // an error code, or M == 0: nothing to do
+  hipStream_t st0 = (hipStream_t)stream;
   if (kernel == PM_K_TILE4 || kernel == PM_K_TILE5) {
     const int rct = pm_linear_bf16_tile_launch(kernel == PM_K_TILE4 ? 4 : 5, x, ldx, x_rows_per_batch, x_batch_stride, w, ldw, bias,
                                                resid, ldr, resid_period, y, ldy, M, N, K, act, ln, st0);
@@ -652,9 +673,7 @@ static int linear_impl(const void* x, int64_t ldx, int64_t x_rows_per_batch, int
   }
   const bool big = kernel == PM_K_PERSIST;
   const int tiles_m = (int)((M + (big ? LBM : BM) - 1) / (big ? LBM : BM)), tiles_n = (int)((N + BN - 1) / BN);
-  const int64_t nblk = (int64_t)tiles_m * tiles_n;
-  if (nblk > 0x7fffffff) return PM_EINVAL;
-  dim3 grid((unsigned)nblk);
+  dim3 grid((unsigned)((int64_t)tiles_m * tiles_n));  // linear_decide checked that it fits
   hipStream_t st = (hipStream_t)stream;
   int rc = (y_dtype == PM_F32)
                ? launch_act<true>(act, big, grid, st, (const bf16*)x, ldx, (const bf16*)w, ldw, bias, resid, ldr,
@@ -715,6 +734,16 @@ extern "C" int pm_linear_bf16_ws(const void* x, int64_t ldx, int64_t x_rows_per_
 }
 
 extern "C" int64_t pm_linear_ws_bytes(void) { return pm_linear_sk_ws_bytes(); }
+
+extern "C" int pm_linear_bf16_plan(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride,
+                                   const void* w, int64_t ldw, const float* bias, const void* resid, int64_t ldr,
+                                   int resid_dtype, int64_t resid_period, const void* y, int64_t ldy, int y_dtype, int64_t M,
+                                   int64_t N, int64_t K, int act, const float* ln_stats, const float* ln_s,
+                                   const float* ln_row_out, const void* ws, int64_t ws_bytes) {
+  PmLnFold ln{ln_stats, ln_s, const_cast<float*>(ln_row_out)};
+  return linear_decide(x, ldx, x_rows_per_batch, x_batch_stride, w, ldw, bias, resid, ldr, resid_dtype, resid_period, y, ldy,
+                       y_dtype, M, N, K, act, ln, ws, ws_bytes, nullptr);
+}
 
 namespace {
 __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats,

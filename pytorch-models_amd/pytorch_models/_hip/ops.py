@@ -144,6 +144,15 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
     LayerNorm fold (pm_linear_bf16_ln): ln_stats (M, 2) + ln_s (N) normalise the input rows in the epilogue;
     want_row_stats=True additionally returns the (M, N/64, 2) partial statistics of the output rows."""
     _cuda(x, w, bias, resid, out)
+    args, out, rows = _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period)
+    M, N, K = args[14:17]
+    rc = _launch("linear_bf16", (2.0 * M * N * K, _linear_bytes(x, w, out, resid)), lambda: lib().pm_linear_bf16_ws(*args, _stream()))
+    check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
+    return (out, rows) if want_row_stats else out
+
+
+def _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period):
+    """The checks of linear() and the arguments of pm_linear_bf16_ws without the stream: (args, out, rows)."""
     _need(x.dim() == 2 and w.dim() == 2 and x.shape[1] == w.shape[1], f"linear: x {tuple(x.shape)} vs w {tuple(w.shape)}")
     _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "linear: x and w must be bf16")
     _need(x.stride(1) == 1 and w.stride(1) == 1, "linear: x and w must be K-contiguous")
@@ -165,15 +174,23 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
         rows = torch.empty((M, N // 64, 2), dtype=torch.float32, device=x.device) if want_row_stats else None
     else:
         rows = None
-    ws, ws_bytes = _ws_args(M, x.device)
-    rc = _launch("linear_bf16", (2.0 * M * N * K, _linear_bytes(x, w, out, resid)), lambda: lib().pm_linear_bf16_ws(
-        x.data_ptr(), x.stride(0), 0, 0, w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
-        resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0,
-        _dt(resid) if resid is not None else 0, resid_period if resid is not None else 0, out.data_ptr(), out.stride(0),
-        _dt(out), M, N, K, ACT[act], ln_stats.data_ptr() if ln_stats is not None else None, ln_s.data_ptr() if ln_s is not None else None,
-        rows.data_ptr() if rows is not None else None, ws, ws_bytes, _stream()))
-    check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
-    return (out, rows) if want_row_stats else out
+    ws, ws_bytes = _ws_args(M, x.device) if x.is_cuda else (None, 0)
+    args = (x.data_ptr(), x.stride(0), 0, 0, w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
+            resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0,
+            _dt(resid) if resid is not None else 0, resid_period if resid is not None else 0, out.data_ptr(), out.stride(0),
+            _dt(out), M, N, K, ACT[act], ln_stats.data_ptr() if ln_stats is not None else None,
+            ln_s.data_ptr() if ln_s is not None else None, rows.data_ptr() if rows is not None else None, ws, ws_bytes)
+    return args, out, rows
+
+
+def linear_plan(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none", resid: Tensor | None = None,
+                out_dtype: torch.dtype = torch.bfloat16, out: Tensor | None = None, ln_stats: Tensor | None = None,
+                ln_s: Tensor | None = None, want_row_stats: bool = False, resid_period: int = 0) -> int:
+    """pm_linear_bf16_plan: the kernel id (1 .. 7) linear() would launch with these operands - the arguments are built by the
+    same function -, 0 for M == 0, or minus the error code.  Host arithmetic only: nothing is launched and the tensors may live
+    on the CPU (pointers are looked at for null and alignment).  PM_GEMM_KERNEL is read once per process."""
+    args, _, _ = _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period)
+    return int(lib().pm_linear_bf16_plan(*args))
 
 
 def linear_f32(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none", resid: Tensor | None = None,
@@ -393,6 +410,15 @@ def linear_strided(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_batch
     x.flat[(m // rows_per_batch) * batch_stride + (m % rows_per_batch) * row_stride : ... + K] (rows may overlap:
     that is how a strided conv window is expressed); resid rows repeat every resid_period rows."""
     _cuda(x, w, bias, resid)
+    args, out = _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out)
+    N = w.shape[0]
+    rc = _launch("linear_bf16", 2.0 * M * N * K, lambda: lib().pm_linear_bf16_ws(*args, _stream()))
+    check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
+    return out
+
+
+def _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out):
+    """The checks of linear_strided() and the arguments of pm_linear_bf16_ws without the stream: (args, out)."""
     _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous() and w.dim() == 2 and w.stride(1) == 1,
           "linear_strided: contiguous bf16 x, K-contiguous bf16 w")
     _need(w.shape[1] == K and rows_per_batch > 0 and M % rows_per_batch == 0, "linear_strided: bad geometry")
@@ -408,15 +434,23 @@ def linear_strided(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_batch
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype, device=x.device)
     else:  # e.g. a column slice of a wider matrix (one group of a grouped conv)
-        _need(out.is_cuda and out.shape == (M, N) and out.stride(1) == 1, "linear_strided: out must be (M, N) with unit column stride")
-    ws, ws_bytes = _ws_args(M, out.device)
-    rc = _launch("linear_bf16", 2.0 * M * N * K, lambda: lib().pm_linear_bf16_ws(
-        x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0),
-        bias.data_ptr() if bias is not None else None, resid.data_ptr() if resid is not None else None,
-        resid.stride(0) if resid is not None else 0, _dt(resid) if resid is not None else 0, resid_period,
-        out.data_ptr(), out.stride(0), _dt(out), M, N, K, ACT[act], None, None, None, ws, ws_bytes, _stream()))
-    check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
-    return out
+        _need(out.shape == (M, N) and out.stride(1) == 1 and (out.is_cuda or not x.is_cuda),
+              "linear_strided: out must be (M, N) with unit column stride")
+    ws, ws_bytes = _ws_args(M, out.device) if out.is_cuda else (None, 0)
+    args = (x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0),
+            bias.data_ptr() if bias is not None else None, resid.data_ptr() if resid is not None else None,
+            resid.stride(0) if resid is not None else 0, _dt(resid) if resid is not None else 0, resid_period,
+            out.data_ptr(), out.stride(0), _dt(out), M, N, K, ACT[act], None, None, None, ws, ws_bytes)
+    return args, out
+
+
+def linear_strided_plan(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_batch: int, batch_stride: int, w: Tensor,
+                        bias: Tensor | None = None, act: str = "none", resid: Tensor | None = None, resid_period: int = 0,
+                        out_dtype: torch.dtype = torch.bfloat16, out: Tensor | None = None) -> int:
+    """linear_plan for the window form: pm_linear_bf16_plan on the arguments linear_strided() would pass (built by the same
+    function).  Host arithmetic only; the tensors may live on the CPU."""
+    args, _ = _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out)
+    return int(lib().pm_linear_bf16_plan(*args))
 
 
 def w2v_stem0(x: Tensor, w: Tensor, bias: Tensor | None, norm: str, gamma: Tensor | None, beta: Tensor | None,

@@ -1,6 +1,8 @@
-"""Randomised shape sweep of pm_linear_bf16 (all three kernels behind one dispatcher: 128x128, 256x128 persistent,
-256x256 persistent) and pm_attention_bf16 against fp32 torch on the same bf16 operands.  Seeded: the same 70 + 24
-cases every run.  Large cases are checked on a sample of rows."""
+"""Randomised shape sweep of pm_linear_bf16 (whatever the dispatcher's cost model picks among the 128x128, the persistent
+256x128, the 256x256 and the (64 MI) x 256 tile kernels: ops.linear_plan tells which - the shape comments below name the
+tile-count thresholds these draws were written for, which the cost model has since replaced) and pm_attention_bf16 against
+fp32 torch on the same bf16 operands.  Seeded: the same 70 + 30 + 24 cases every run.  Large cases are checked on a sample of
+rows.  Which kernel a given shape reaches, with derived bounds, is the business of tests/test_hip_linear_adversarial.py."""
 import math
 import random
 
@@ -20,11 +22,11 @@ def _cases(n, seed):
         kind = rng.random()
         if kind < 0.35:  # small / ragged: the 128x128 kernel
             M, N, K = rng.randint(1, 700), rng.choice([8, 24, 100, 132, 200, 333, 512, 1000]), 8 * rng.randint(1, 40)
-        elif kind < 0.7:  # the 256x128 persistent kernel (>= 512 tiles, M >= 4096)
+        elif kind < 0.7:  # written for the 256x128 persistent kernel's old threshold (>= 512 tiles, M >= 4096)
             N = rng.choice([128, 384, 512, 768, 1024])
             M = rng.randint(512 * 256 * 128 // N // 1 + 1, 512 * 256 * 128 // N + 9000) if N < 1024 else rng.randint(20000, 40000)
             K = 64 * rng.randint(1, 12)
-        else:  # the 256x256 persistent kernel (>= 1024 tiles)
+        else:  # written for the 256x256 kernel's old threshold (>= 1024 tiles): today mostly the tile kernels (M % 8 == 0) or it
             N = rng.choice([1536, 2048, 2304, 3072, 1032])
             M = 1024 * 256 * 256 // N + rng.randint(1, 9000)
             K = 64 * rng.randint(1, 8)
