@@ -17,9 +17,14 @@
 // the waveform, so per clip  sum_t v[c, t] = sum_j w[c, j] S[j]  and  sum_t v[c, t]^2 = sum_{j, j'} w[c, j] w[c, j'] R[j][j']
 // with S[j] = sum_t x[s t + j] and R[j][j'] = sum_t x[s t + j] x[s t + j'] - 10 + 55 numbers per clip, whatever C0 is.
 // One pass over the waveform (640 KB per 10 s clip) accumulates them per 1024-step chunk in a fixed order (no atomics:
-// bit-reproducible), a finalize kernel folds the chunks in fp64 and evaluates the two forms per channel, centred
+// bit-reproducible), a finalize kernel folds the chunks and evaluates the two forms per channel, centred
 // (variance = w^T (R/T - s s^T) w), into (mean, rstd); the normalising pass then computes the conv once.  (The first
-// version recomputed the conv for the statistics: 189 us + 37 us at 32 x 10 s; this one takes ~15 us.)
+// version recomputed the conv for the statistics: 189 us + 37 us at 32 x 10 s.)
+// The centred form cancels: its error is (rounding of the sums) x (A / sigma)^2 with A = sum |w| |x|, second order in the
+// condition number, where normalising the computed conv output is first order.  With fp32 sums a zero-sum filter on a
+// waveform with a large slow component (A / sigma ~ 3e3) lost a third of its variance, so S and R are
+// accumulated in fp64 from the first addition on: a product of two fp32 values is exact in fp64, and the sums carry
+// 2^-53 (A / sigma)^2.  The partials are doubles in the caller's scratch (pm_w2v_stem0_scratch_floats counts them as floats).
 #include "common.h"
 
 namespace {
@@ -28,7 +33,13 @@ constexpr int TCH = 256;  // time steps per workgroup of the conv pass
 
 enum { MODE_NONE = 0, MODE_LAYERNORM = 1, MODE_INSTANCE = 2 };
 constexpr int ACH = 1024;      // time steps per workgroup of the autocorrelation pass
-constexpr int APART = 80;      // floats per (clip, chunk) partial: KT sums + KT (KT + 1) / 2 products, padded
+constexpr int APART = 80;      // doubles per (clip, chunk) partial: KT sums + KT (KT + 1) / 2 products, padded
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 template <int KT, int MODE>
 __global__ __launch_bounds__(256) void w2v_stem0_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -126,29 +137,29 @@ __global__ __launch_bounds__(256) void w2v_stem0_kernel(const float* __restrict_
   }
 }
 
-// (S, R) of one ACH-step chunk of one clip: thread-private sums over its steps, then a fixed-order wave / workgroup fold
+// (S, R) of one ACH-step chunk of one clip in fp64: thread-private sums over its steps, then a fixed-order wave / workgroup fold
 template <int KT>
-__global__ __launch_bounds__(256) void w2v_autocorr_kernel(const float* __restrict__ x, float* __restrict__ partials, int64_t L,
+__global__ __launch_bounds__(256) void w2v_autocorr_kernel(const float* __restrict__ x, double* __restrict__ partials, int64_t L,
                                                            int T0, int stride, int nchunk) {
   constexpr int NP = KT + KT * (KT + 1) / 2;
-  __shared__ float red[4][NP];
+  __shared__ double red[4][NP];
   const int b = blockIdx.y, chunk = blockIdx.x;
   const float* xb = x + (int64_t)b * L;
-  float acc[NP];
+  double acc[NP];
 #pragma unroll
-  for (int p = 0; p < NP; ++p) acc[p] = 0.f;
+  for (int p = 0; p < NP; ++p) acc[p] = 0.0;
   const int t_end = min((chunk + 1) * ACH, T0);
   for (int t = chunk * ACH + threadIdx.x; t < t_end; t += 256) {
-    float xv[KT];
+    double xv[KT];
 #pragma unroll
-    for (int j = 0; j < KT; ++j) xv[j] = xb[(int64_t)t * stride + j];
+    for (int j = 0; j < KT; ++j) xv[j] = (double)xb[(int64_t)t * stride + j];
     int p = KT;
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
       acc[j] += xv[j];
 #pragma unroll
       for (int j2 = j; j2 < KT; ++j2) {
-        acc[p] = fmaf(xv[j], xv[j2], acc[p]);
+        acc[p] = fma(xv[j], xv[j2], acc[p]);
         ++p;
       }
     }
@@ -156,7 +167,7 @@ __global__ __launch_bounds__(256) void w2v_autocorr_kernel(const float* __restri
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
-    const float v = wave_sum(acc[p]);
+    const double v = wave_sum_f64(acc[p]);
     if (lane == 0) red[wave][p] = v;
   }
   __syncthreads();
@@ -166,9 +177,9 @@ __global__ __launch_bounds__(256) void w2v_autocorr_kernel(const float* __restri
   }
 }
 
-// one workgroup per clip: fold the chunks in fp64, then per channel mean = w.S / T0 (+ bias) and the centred variance
+// one workgroup per clip: fold the chunks, then per channel mean = w.S / T0 (+ bias) and the centred variance
 template <int KT>
-__global__ __launch_bounds__(256) void w2v_stats_finalize_kernel(const float* __restrict__ partials, const float* __restrict__ w,
+__global__ __launch_bounds__(256) void w2v_stats_finalize_kernel(const double* __restrict__ partials, const float* __restrict__ w,
                                                                  const float* __restrict__ bias, float* __restrict__ stats, int C0,
                                                                  int nchunk, int T0, float eps) {
   constexpr int NP = KT + KT * (KT + 1) / 2;
@@ -176,7 +187,7 @@ __global__ __launch_bounds__(256) void w2v_stats_finalize_kernel(const float* __
   const int b = blockIdx.x;
   if (threadIdx.x < NP) {
     double s = 0.0;
-    for (int k = 0; k < nchunk; ++k) s += (double)partials[((int64_t)b * nchunk + k) * APART + threadIdx.x];
+    for (int k = 0; k < nchunk; ++k) s += partials[((int64_t)b * nchunk + k) * APART + threadIdx.x];
     tot[threadIdx.x] = s / T0;
   }
   __syncthreads();
@@ -221,7 +232,10 @@ __global__ __launch_bounds__(256) void group_windows_kernel(const void* __restri
   if (t >= 0 && t < T) {
     const int64_t src = (b * T + t) * ldx + (int64_t)g * cg;
     if ((cg & 7) == 0) {
-      if constexpr (XF32) {
+      // chunks at or past cg stay zero: with cgp - cg >= 8 they would otherwise copy the next group's channels (and read
+      // past the last row's end)
+      if (ch * 8 >= cg) {
+      } else if constexpr (XF32) {
         const f32x4 a = *(const f32x4*)((const float*)x + src + ch * 8), c = *(const f32x4*)((const float*)x + src + ch * 8 + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { o[e] = (bf16)a[e]; o[4 + e] = (bf16)c[e]; }
@@ -267,7 +281,7 @@ int launch_stem0(int k, dim3 grid, hipStream_t st, const float* x, const float* 
 
 }  // namespace
 
-extern "C" int64_t pm_w2v_stem0_scratch_floats(int64_t B, int64_t T0) { return B * ((T0 + ACH - 1) / ACH) * APART; }
+extern "C" int64_t pm_w2v_stem0_scratch_floats(int64_t B, int64_t T0) { return 2 * B * ((T0 + ACH - 1) / ACH) * APART; }
 
 extern "C" int pm_w2v_stem0(const float* x, const float* w, const float* bias, int norm, const float* gamma, const float* beta,
                             float eps, float* partials, float* stats, void* out, int64_t B, int64_t L, int64_t C0, int64_t k,
@@ -280,6 +294,7 @@ extern "C" int pm_w2v_stem0(const float* x, const float* w, const float* bias, i
   if (L < k) return PM_EINVAL;
   if (C0 % 8 || C0 > 512 || k != 10) return PM_EUNSUPPORTED;
   if ((uintptr_t)out & 15) return PM_EALIGN;
+  if (norm == PM_W2V_NORM_INSTANCE && ((uintptr_t)partials & 7)) return PM_EALIGN;  // the partials are doubles
   const int64_t T0 = (L - k) / stride + 1;
   const int64_t nchunk = (T0 + TCH - 1) / TCH;
   if (T0 > 0x7fffffff / 8 || B > 65535) return PM_EINVAL;
@@ -288,9 +303,9 @@ extern "C" int pm_w2v_stem0(const float* x, const float* w, const float* bias, i
   int rc;
   if (norm == PM_W2V_NORM_INSTANCE) {
     const int na = (int)((T0 + ACH - 1) / ACH);
-    hipLaunchKernelGGL((w2v_autocorr_kernel<10>), dim3((unsigned)na, (unsigned)B), dim3(256), 0, st, x, partials, L, (int)T0,
+    hipLaunchKernelGGL((w2v_autocorr_kernel<10>), dim3((unsigned)na, (unsigned)B), dim3(256), 0, st, x, (double*)partials, L, (int)T0,
                        (int)stride, na);
-    hipLaunchKernelGGL((w2v_stats_finalize_kernel<10>), dim3((unsigned)B), dim3(256), 0, st, partials, w, bias, stats, (int)C0, na,
+    hipLaunchKernelGGL((w2v_stats_finalize_kernel<10>), dim3((unsigned)B), dim3(256), 0, st, (const double*)partials, w, bias, stats, (int)C0, na,
                        (int)T0, eps);
     rc = launch_stem0<MODE_INSTANCE>((int)k, grid, st, x, w, bias, gamma, beta, stats, eps, (bf16*)out, L, (int)T0, (int)C0,
                                      (int)stride);

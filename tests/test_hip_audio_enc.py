@@ -5,7 +5,10 @@ end to end against the oracle on the same bf16-rounded weights and against the r
 
 Tolerances: kernels that compute in fp32 and round once to bf16: |err| <= 4e-3 |want| + 1e-3 (one bf16 ulp is 3.9e-3
 relative); GEMM-backed pieces and whole models: rel-L2 <= 2e-2 vs the oracle, 3e-2 vs the reference golden (fp32
-weights), as in test_hip_blocks.py."""
+weights), as in test_hip_blocks.py.
+
+The element-wise float64 parity of pm_w2v_stem0, pm_group_windows, pm_grouped_conv_bf16 and pm_avgpool_time2 (derived bounds, exact
+integer families, ill-conditioned InstanceNorm statistics) is tests/test_hip_audio_adversarial.py (tests/audio_cases.py)."""
 import pytest
 import torch
 

@@ -7,6 +7,9 @@ Tolerances (stated):
   O(1) data; log-mel uses atol 2e-5 on the (x+4)/4 scale... we allow 1e-4 where log10 amplifies tiny bins).
 * encoder / decoder (bf16 activations, fp32 accumulate) vs the fp32 oracle on bf16-rounded weights:
   rel-L2 <= 2e-2 on LayerNorm-ed outputs, logits rel-L2 <= 3e-2.
+
+Kernel-level parity of the front end - pm_stft_mel / pm_stft_mel_folded / pm_logmel_finalize at other geometries than (400, 160),
+pm_whisper_stem1 tap by tap, each against float64 with derived bounds - is tests/test_hip_audio_adversarial.py (tests/audio_cases.py).
 """
 import pytest
 import torch
