@@ -641,8 +641,8 @@ int pm_rvq_decode_f32(const int64_t* codes, int64_t stride_b, int64_t stride_q, 
                       float* out, int64_t B, int64_t T, int64_t n_q, int64_t dim, int64_t codebook_size, void* stream);
 
 /* pm_groupnorm1_f32: GroupNorm(1, C) of B clips in place: x (B, n) with n = T * C time-major (channel = index % C), biased
- * variance over the whole clip, per-channel affine, + resid (B, n) when not NULL.  Partial sums of 64 floats per thread in fp32,
- * combined in fp64.  work: pm_groupnorm1_workspace_doubles(B, n) doubles.  B <= 65535. */
+ * variance over the whole clip, per-channel affine, + resid (B, n) when not NULL.  Per thread the fp32 mean of 64 floats and their
+ * centred sums, combined in fp64 (Chan): no (mean / sigma)^2 error.  work: pm_groupnorm1_workspace_doubles(B, n) doubles.  B <= 65535. */
 int pm_groupnorm1_f32(float* x, const float* gamma, const float* beta, const float* resid, double* work, int64_t B, int64_t n,
                       int64_t C, float eps, void* stream);
 int64_t pm_groupnorm1_workspace_doubles(int64_t B, int64_t n);

@@ -14,7 +14,7 @@
 //                       frame t - 1 beside layer 0 at frame t (T + 1 launches).  No grid barrier, no flag.
 //  pm_rvq_encode_f32    all stages of the residual vector quantizer in one pass over the latent rows.
 //  pm_rvq_decode_f32    sum of the chosen codebook rows, time-major.
-//  pm_groupnorm1_f32    GroupNorm(1, C) over a whole clip (fp64 combination of fp32 partial sums), in place.
+//  pm_groupnorm1_f32    GroupNorm(1, C) over a whole clip (per-thread fp32 mean and centred squares, combined in fp64), in place.
 //  pm_encodec_scale_f32 / pm_scale_clips_f32   the 48 kHz variant's per-clip input scale and its division / multiplication.
 #include "common.h"
 
@@ -402,7 +402,8 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ GroupNorm(1, C), scale
-constexpr int GN_CHUNK = 16384;  // floats per workgroup: 64 per thread in fp32, everything above that in fp64
+constexpr int GN_CHUNK = 16384;  // floats per workgroup: 64 per thread in fp32 around the thread's own mean, everything above in fp64
+constexpr int GN_PER = GN_CHUNK / 256;
 
 __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   const int tid = threadIdx.x;
@@ -417,22 +418,47 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   return s;
 }
 
+// Statistics of one chunk as (mean, M2 = sum (x - mean)^2), the two doubles of the chunk.  This kernel used to store the fp32 sums
+// S = sum x and SS = sum x^2 of 64 values per thread and gn_apply_kernel formed SS / n - mean^2: at |mean| / sigma = 4096 the fp32
+// SS carries an error of about 64 u mean^2 per value, a thousand times the variance, and the output was no normalisation at all
+// (tests/encodec_cases.py, the offset family, found it).  Now a thread keeps its 64 values in registers, takes their fp32 mean p as a
+// pivot and sums d = sum (x - p) and q = sum (x - p)^2 in fp32 (small numbers whatever the clip's mean); its exact-arithmetic
+// statistics are mean_t = p + d / n_t and M2_t = q - d^2 / n_t, formed in fp64, and threads, then chunks, are combined in fp64 with
+// Chan's formula M2 = sum (M2_i + n_i (mean_i - mean)^2).
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, double* __restrict__ part, int64_t n,
                                                        int nchunk) {
   __shared__ double sh[256];
   const int64_t b = blockIdx.y, beg = (int64_t)blockIdx.x * GN_CHUNK;
   const int64_t end = beg + GN_CHUNK < n ? beg + GN_CHUNK : n;
   const float* xb = x + b * n;
-  float s = 0.f, ss = 0.f;
-  for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
-    const float v = xb[i];
-    s += v;
-    ss = fmaf(v, v, ss);
+  float v[GN_PER];
+  float s = 0.f;
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < GN_PER; ++j) {
+    const int64_t i = beg + threadIdx.x + j * 256;
+    const bool in = i < end;
+    v[j] = in ? xb[i] : 0.f;
+    s += v[j];
+    cnt += in;
   }
-  const double S = block_sum_f64((double)s, sh), SS = block_sum_f64((double)ss, sh);
+  const float p = cnt ? s / (float)cnt : 0.f;
+  float d = 0.f, q = 0.f;
+#pragma unroll
+  for (int j = 0; j < GN_PER; ++j) {
+    const float c = beg + threadIdx.x + j * 256 < end ? v[j] - p : 0.f;
+    d += c;
+    q = fmaf(c, c, q);
+  }
+  const double nt = (double)cnt;
+  const double mean_t = cnt ? (double)p + (double)d / nt : 0.0;
+  const double m2_t = cnt ? (double)q - (double)d * (double)d / nt : 0.0;
+  const double mean = block_sum_f64(nt * mean_t, sh) / (double)(end - beg);
+  const double dm = mean_t - mean;
+  const double M2 = block_sum_f64(m2_t + nt * dm * dm, sh);
   if (threadIdx.x == 0) {
-    part[(b * nchunk + blockIdx.x) * 2] = S;
-    part[(b * nchunk + blockIdx.x) * 2 + 1] = SS;
+    part[(b * nchunk + blockIdx.x) * 2] = mean;
+    part[(b * nchunk + blockIdx.x) * 2 + 1] = M2 > 0.0 ? M2 : 0.0;
   }
 }
 
@@ -441,15 +467,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(float* __restrict__ x, co
                                                        const float* __restrict__ resid, int64_t n, int C, int nchunk, float eps) {
   __shared__ double sh[256];
   const int64_t b = blockIdx.y;
-  double s = 0.0, ss = 0.0;
+  auto count = [&](int i) { return (double)(i + 1 < nchunk ? (int64_t)GN_CHUNK : n - (int64_t)i * GN_CHUNK); };
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nchunk; i += 256) s += count(i) * part[(b * nchunk + i) * 2];
+  const double mean = block_sum_f64(s, sh) / (double)n;
+  double m2 = 0.0;
   for (int i = threadIdx.x; i < nchunk; i += 256) {
-    s += part[(b * nchunk + i) * 2];
-    ss += part[(b * nchunk + i) * 2 + 1];
+    const double dm = part[(b * nchunk + i) * 2] - mean;
+    m2 += part[(b * nchunk + i) * 2 + 1] + count(i) * dm * dm;
   }
-  const double S = block_sum_f64(s, sh), SS = block_sum_f64(ss, sh);
-  const double mean = S / (double)n;
-  double var = SS / (double)n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
+  const double var = block_sum_f64(m2, sh) / (double)n;
   const float mu = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
   const int64_t beg = (int64_t)blockIdx.x * GN_CHUNK;
   const int64_t end = beg + GN_CHUNK < n ? beg + GN_CHUNK : n;

@@ -4,7 +4,7 @@
 In scope (through pytorch_models._hip.ops, the poison family through the C ABI): w2v_stem0 (norm none / layer / instance),
 whisper_stem1, grouped_conv (act none / gelu, bias, resid), group_windows, avgpool_time2, and - in the second half of the file, with
 their own case type - stft_mel in its three modes (pm_stft_mel, pm_stft_mel_folded, pm_logmel_finalize).
-Out of scope: rmsnorm / geglu / embed_tokens (the T5 and ragged suites), EnCodec's conv1d_f32, the strided-window GEMM layers of the
+Out of scope: rmsnorm / geglu / embed_tokens (the T5 and ragged suites), EnCodec's kernels (tests/encodec_cases.py), the strided-window GEMM layers of the
 feature encoder (tests/linear_cases.py).
 
 Contract (DESIGN.md, "2e. Audio front-end numerics contract").

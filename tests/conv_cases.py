@@ -3,7 +3,7 @@
 
 In scope (through pytorch_models._hip.ops): conv_bf16, resnet_stem, dwconv7_ln, convnext_stem, dwconv3_bn_act (y, psum, gate,
 write_y=False), maxvit_stem, im2col3x3, avgpool2x2, conv2d_nhwc (dense, grouped, depthwise; act none / relu / silu; resid).
-Out of scope: EnCodec's conv1d_f32 and its transposed form (already tested against fp64, tests/test_hip_encodec.py); the 1-D
+Out of scope: EnCodec's conv1d_f32 and its transposed form (the same treatment in tests/encodec_cases.py); the 1-D
 grouped_conv and the wav2vec2 and Whisper stems have the same treatment in tests/audio_cases.py.
 
 Contract (DESIGN.md, "2c. Convolution numerics contract").
