@@ -708,6 +708,19 @@ int pm_cls_attend_supported(int64_t L, int64_t d, int64_t H);
 int pm_cls_head_gemm(const void* x, int64_t ldx, int64_t x_group_stride, const void* w, const float* bias, void* y, int64_t ldy,
                      int64_t y_group_stride, int64_t M, int64_t N, int64_t K, int64_t G, void* stream);
 
+/* ---- Sequence scoring (csrc/lm_score.hip): the vocabulary projection with the logits consumed in registers.  With
+ * x[m, v] = sum_k h[m, k] w[v, k] (fp32 accumulation): lse[m] = log sum_{v < V} exp(x[m, v]), logprob[m] = x[m, targets[m]] - lse[m],
+ * argmax[m] = the LOWEST index among the maxima of x[m, :V].  The (M, V) matrix is never stored.
+ *   h bf16 (M, K), row stride ldh; w bf16 (V, K), row stride ldw (elements, both % 8, bases 16-byte aligned: else PM_EALIGN);
+ *   targets int64 (M) in [-1, V): -1 (and any id outside [0, V): a bad id cannot fault; callers validate the range) means "ignore":
+ *   logprob[m] = 0, lse and argmax are still written.  logprob f32 (M); lse f32 (M) or NULL; argmax int32 (M) or NULL;
+ *   ws: pm_lm_score_ws_bytes(M, V) bytes (20 per row and 2048-column vocabulary chunk), 4-byte aligned, no initial state.
+ *   K % 8 == 0 (else PM_EUNSUPPORTED); any M, V, K >= 1 otherwise.  No atomics; chunking and merge order depend on V alone, so a
+ *   row's outputs are bit-identical wherever the row sits in the batch and whatever M is. */
+int pm_lm_score_bf16(const void* h, int64_t ldh, const void* w, int64_t ldw, const int64_t* targets, float* logprob, float* lse,
+                     int32_t* argmax, void* ws, int64_t M, int64_t V, int64_t K, void* stream);
+int64_t pm_lm_score_ws_bytes(int64_t M, int64_t V);
+
 #ifdef __cplusplus
 }
 #endif

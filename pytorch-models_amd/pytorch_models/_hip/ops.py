@@ -1528,3 +1528,55 @@ def cls_attend(x: Tensor, stats: Tensor | None, u: Tensor, scale: float, eps: fl
         N, L, d, H, float(scale), float(eps), _stream()))
     check(rc, f"pm_cls_attend(N={N}, L={L}, d={d}, H={H})")
     return out
+
+
+# ---- sequence scoring (csrc/lm_score.hip) ----
+LM_SCORE_CHECK_IDS = True  # lm_score validates the targets against [-1, V) (one read-back per eager call, as embed_tokens does)
+
+
+def lm_score_ws_bytes(M: int, V: int) -> int:
+    return int(lib().pm_lm_score_ws_bytes(M, V))
+
+
+def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, want_argmax: bool = False, out: Tensor | None = None,
+             lse_out: Tensor | None = None, argmax_out: Tensor | None = None, ws: Tensor | None = None):
+    """pm_lm_score_bf16: h bf16 (M, K), w bf16 (V, K) (unit last strides, row strides % 8), targets int64 (M) in [-1, V) ->
+    logprob f32 (M): x[m, targets[m]] - log sum_v exp(x[m, v]) for x = h @ w.T in fp32, 0 where the target is -1 ("ignore");
+    with want_lse the f32 (M) log-sum-exp, with want_argmax the int32 (M) lowest arg-max index: (logprob[, lse][, argmax]).
+    The (M, V) logits are never stored: the only scratch is lm_score_ws_bytes(M, V) bytes (20 per row and 2048 columns).
+    ``out`` / ``lse_out`` / ``argmax_out`` / ``ws`` (uint8): caller-owned contiguous buffers instead of new ones."""
+    _cuda(h, w, targets, out, lse_out, argmax_out, ws)
+    _need(h.dim() == 2 and w.dim() == 2 and h.shape[1] == w.shape[1], f"lm_score: h {tuple(h.shape)} vs w {tuple(w.shape)}")
+    _need(h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "lm_score: h and w must be bf16")
+    _need(h.stride(1) == 1 and w.stride(1) == 1, "lm_score: h and w must be K-contiguous")
+    M, K = h.shape
+    V = w.shape[0]
+    _need(M >= 1 and V >= 1 and K >= 1, "lm_score: empty operand")
+    _need(h.stride(0) % 8 == 0 and w.stride(0) % 8 == 0, "lm_score: row strides must be multiples of 8 elements")
+    _need(targets.dtype == torch.int64 and targets.shape == (M,), f"lm_score: targets must be int64 ({M},)")
+    targets = targets.contiguous()
+    if LM_SCORE_CHECK_IDS and not torch.cuda.is_current_stream_capturing():
+        bad = (targets < -1) | (targets >= V)
+        if bool(bad.any()):
+            raise IndexError(f"lm_score: target id {targets[bad][0].item()} outside [-1, {V})")
+    dev = h.device
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=dev)
+    _need(out.dtype == torch.float32 and out.shape == (M,) and out.is_contiguous(), "lm_score: out must be contiguous f32 (M,)")
+    lse = lse_out if lse_out is not None else (torch.empty(M, dtype=torch.float32, device=dev) if want_lse else None)
+    am = argmax_out if argmax_out is not None else (torch.empty(M, dtype=torch.int32, device=dev) if want_argmax else None)
+    if lse is not None:
+        _need(lse.dtype == torch.float32 and lse.shape == (M,) and lse.is_contiguous(), "lm_score: lse_out must be contiguous f32 (M,)")
+    if am is not None:
+        _need(am.dtype == torch.int32 and am.shape == (M,) and am.is_contiguous(), "lm_score: argmax_out must be contiguous int32 (M,)")
+    nws = lm_score_ws_bytes(M, V)
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws, f"lm_score: ws must hold {nws} bytes")
+    nbytes = float(2 * (h.numel() + w.numel()) + nws + 8 * M + 4 * M)
+    rc = _launch("lm_score", (2.0 * M * V * K, nbytes), lambda: lib().pm_lm_score_bf16(
+        h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), targets.data_ptr(), out.data_ptr(),
+        lse.data_ptr() if lse is not None else None, am.data_ptr() if am is not None else None, ws.data_ptr(), M, V, K, _stream()))
+    check(rc, f"pm_lm_score_bf16(M={M}, V={V}, K={K})")
+    res = (out,) + ((lse,) if want_lse or lse_out is not None else ()) + ((am,) if want_argmax or argmax_out is not None else ())
+    return res[0] if len(res) == 1 else res

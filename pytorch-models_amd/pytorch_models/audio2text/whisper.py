@@ -110,10 +110,37 @@ class WhisperDecoder(nn.Module):
             E = self.token_embs.weight
             h = self.norm(self.layers(ops.embed_tokens(x, E, self.pos_embs), memory.float()))
             return ops.linear_f32(h.view(-1, h.shape[-1]), E).view(*x.shape, E.shape[0])
+        h, E = self.hidden_rows(x, memory)
+        return ops.linear(h.view(-1, h.shape[-1]), E, None, out_dtype=torch.float32).view(*x.shape, E.shape[0])
+
+    def hidden_rows(self, x: Tensor, memory: Tensor):
+        """bf16 parameters: (hidden rows (B, L, d) bf16, head weights (V, d) bf16) - what forward's last GEMM and score's
+        kernel both read."""
         E = _wb(self.token_embs, "E", self.token_embs.weight)
         h = ops.embed_tokens(x, E, _f32(self, "pos", self.pos_embs))  # (B, L, d) bf16
-        h = self.norm(self.layers(h, memory))
-        return ops.linear(h.view(-1, h.shape[-1]), E, None, out_dtype=torch.float32).view(*x.shape, E.shape[0])
+        return self.norm(self.layers(h, memory)), E
+
+    @torch.no_grad()
+    def score(self, tokens: Tensor, memory: Tensor, lengths=None, *, return_argmax: bool = False):
+        """Teacher-forced scoring in O(B L) memory: tokens (B, L) int64 - the decoder's input ids, exactly what forward takes -
+        and memory (B, S, d) -> (B, L - 1) fp32 with out[b, t] = log p(tokens[b, t + 1] | tokens[b, : t + 1], memory[b]).
+        ``lengths`` (B,), 1 <= len_b <= L, marks a right-padded batch: positions with t + 1 >= len_b are ignored and return 0, so
+        out.sum(-1) is the sequence log-likelihood and out.sum(-1) / (lengths - 1) Whisper's avg_logprob.  ``return_argmax``:
+        also the (B, L - 1) int64 greedy predictions.  bf16 parameters on a HIP device: projection, log-softmax and gather are
+        one kernel (ops.lm_score), the (B, L, V) logits are never stored.  A module and inputs that both live on the CPU take
+        the plain-torch form: fp32 log_softmax of forward's logits and a gather."""
+        from ..text.gpt2 import score_gate, score_rows, score_targets
+
+        if _cpu.on_cpu(tokens, self.token_embs.weight):
+            tgt = score_targets(tokens, lengths, "WhisperDecoder.score")
+            logits = self.forward(tokens, memory)[:, :-1].float()
+            lp = torch.log_softmax(logits, -1).gather(-1, tgt.clamp(min=0).unsqueeze(-1)).squeeze(-1)
+            lp = torch.where(tgt >= 0, lp, torch.zeros_like(lp))
+            return (lp, logits.argmax(-1)) if return_argmax else lp
+        score_gate("WhisperDecoder.score", self.token_embs.weight, tokens, memory)
+        score_targets(tokens, lengths, "WhisperDecoder.score")  # shape and lengths errors before any launch
+        h, E = self.hidden_rows(tokens, memory)
+        return score_rows(h, E, tokens, lengths, return_argmax, "WhisperDecoder.score")
 
     @torch.no_grad()
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
@@ -161,6 +188,13 @@ class Whisper(nn.Module):
 
     def forward(self, x: Tensor, targets: Tensor) -> Tensor:
         return self.decoder(targets, self.encoder(x))
+
+    @torch.no_grad()
+    def score(self, x: Tensor, tokens: Tensor, lengths=None, *, return_argmax: bool = False):
+        """log-mel (B, n_mels, T) + decoder input ids (B, L) -> (B, L - 1) fp32 log-probabilities of tokens[b, t + 1] given
+        tokens[b, : t + 1] and the clip (WhisperDecoder.score's convention: ``lengths`` for a right-padded batch, ignored positions
+        return 0, ``return_argmax`` adds the greedy predictions)."""
+        return self.decoder.score(tokens, self.encoder(x), lengths, return_argmax=return_argmax)
 
     @torch.no_grad()
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",

@@ -6,7 +6,7 @@ import torch
 from torch import Tensor, nn
 
 from ..transformer import Decoder
-from .gpt2 import _lm_forward
+from .gpt2 import _lm_forward, _lm_hidden, _lm_score
 
 
 class GPT(nn.Module):
@@ -22,6 +22,18 @@ class GPT(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         """token ids (..., L) int64 -> logits (..., L, 40478) fp32 (gpt.py:24-29)."""
         return _lm_forward(self, x, None)
+
+    def hidden_rows(self, tokens: Tensor):
+        """(hidden rows (B, L, d) bf16, head weights (V, d) bf16): what forward's last GEMM and score's kernel both read."""
+        return _lm_hidden(self, tokens, None)
+
+    @torch.no_grad()
+    def score(self, tokens: Tensor, lengths=None, *, return_argmax: bool = False):
+        """Teacher-forced scoring, GPT2.score's convention: tokens (B, L) int64 -> (B, L - 1) fp32,
+        out[b, t] = log p(tokens[b, t + 1] | tokens[b, : t + 1]); ``lengths`` marks a right-padded batch (ignored positions
+        return 0); ``return_argmax`` adds the (B, L - 1) int64 greedy predictions.  bf16 parameters on a HIP device; the
+        (B, L, 40478) logits are never stored."""
+        return _lm_score(self, tokens, None, lengths, return_argmax, "GPT.score")
 
     @staticmethod
     def from_openai(*, pretrained=False, **kwargs) -> "GPT":

@@ -3,7 +3,9 @@ names token_embs, pos_embs, layers, norm).
 
 forward = pm_embed_tokens (token + position rows in one kernel) -> Decoder of pre-norm, causal, tanh-GELU layers
 (transformer.py) -> LayerNorm -> logits against the tied embedding matrix (pm_linear_bf16, fp32 out, ragged N = 50257).
-Greedy generation with a KV cache: GPT2.generate / text.DecoderGenerator (generate.py's decode-step kernels)."""
+Greedy generation with a KV cache: GPT2.generate / text.DecoderGenerator (generate.py's decode-step kernels).
+Teacher-forced scoring: GPT2.score = the same hidden rows -> pm_lm_score_bf16 (projection, log-softmax and gather in one kernel; the
+logits are never stored).  score_rows / score_targets / score_gate below are the scoring tail every model's ``score`` shares."""
 from __future__ import annotations
 
 import torch
@@ -24,13 +26,69 @@ def _lm_forward(m, tokens: Tensor, final_norm) -> Tensor:
         if final_norm is not None:
             h = final_norm(h)
         return ops.linear_f32(h.view(-1, h.shape[-1]), E).view(*lead, E.shape[0])
+    h, E = _lm_hidden(m, tok2, final_norm)
+    logits = ops.linear(h.view(-1, h.shape[-1]), E, None, out_dtype=torch.float32)
+    return logits.view(*lead, E.shape[0])
+
+
+def _lm_hidden(m, tok2: Tensor, final_norm):
+    """bf16 parameters: the hidden rows (B, L, d) the vocabulary projection reads, and its (V, d) weights.  forward and score
+    both start here."""
     E = m.token_embs.weight
     h = ops.embed_tokens(tok2, E, _f32(m, "pos", m.pos_embs))
     h = m.layers(h)
     if final_norm is not None:
         h = final_norm(h)
-    logits = ops.linear(h.view(-1, h.shape[-1]), E, None, out_dtype=torch.float32)
-    return logits.view(*lead, E.shape[0])
+    return h, E
+
+
+def score_gate(who: str, w: Tensor, *inputs: Tensor) -> None:
+    """Device and dtype rule of every ``score``: operands on one HIP device (the device error first, as forward raises it), bf16
+    parameters."""
+    ops.check_devices(w, *inputs)
+    if w.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{who}: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda()); fp32 parameters "
+                                  "score through forward() and torch.log_softmax")
+
+
+def score_targets(tokens: Tensor, lengths, who: str) -> Tensor:
+    """The (B, L - 1) int64 targets of teacher-forced scoring: tokens[b, t + 1], or -1 ("ignore") where t + 1 >= len_b."""
+    if tokens.dim() != 2 or tokens.dtype != torch.int64:
+        raise ValueError(f"{who}: tokens must be int64 (B, L), got {tokens.dtype} {tuple(tokens.shape)}")
+    B, L = tokens.shape
+    tgt = tokens[:, 1:]
+    if lengths is None:
+        return tgt.contiguous()
+    lens = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
+    if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > L:
+        raise ValueError(f"{who}: lengths must hold {B} values in [1, {L}], got {lens.tolist()}")
+    keep = torch.arange(1, L, device=tokens.device)[None, :] < lens.to(tokens.device)[:, None]
+    return torch.where(keep, tgt, torch.full_like(tgt, -1))
+
+
+def score_rows(h: Tensor, W: Tensor, tokens: Tensor, lengths, return_argmax: bool, who: str):
+    """THE scoring tail of every model: hidden rows h (B, L, d) bf16 (what forward multiplies by W), head weights W (V, d) bf16,
+    decoder input ids tokens (B, L) -> out (B, L - 1) f32, out[b, t] = log p(tokens[b, t + 1] | tokens[b, : t + 1]); positions
+    with t + 1 >= lengths[b] are ignored and return exactly 0, so out.sum(-1) is the sequence log-likelihood.  With
+    return_argmax also the (B, L - 1) int64 greedy predictions (the lowest arg-max index of each position's logits).  One
+    ops.lm_score launch over the B (L - 1) rows: nothing of size rows x V is allocated."""
+    tgt = score_targets(tokens, lengths, who)
+    B, L = tokens.shape
+    if L == 1:
+        out = torch.zeros((B, 0), dtype=torch.float32, device=h.device)
+        return (out, torch.zeros((B, 0), dtype=torch.int64, device=h.device)) if return_argmax else out
+    rows = h[:, :-1].reshape(B * (L - 1), h.shape[-1])  # the last position predicts nothing that is scored
+    res = ops.lm_score(rows, W, tgt.reshape(-1), want_argmax=return_argmax)
+    if return_argmax:
+        return res[0].view(B, L - 1), res[1].to(torch.int64).view(B, L - 1)
+    return res.view(B, L - 1)
+
+
+def _lm_score(m, tokens: Tensor, final_norm, lengths, return_argmax: bool, who: str):
+    score_gate(who, m.token_embs.weight, tokens)
+    score_targets(tokens, lengths, who)  # shape and lengths errors before any launch
+    h, E = _lm_hidden(m, tokens, final_norm)
+    return score_rows(h, E, tokens, lengths, return_argmax, who)
 
 
 class GPT2(nn.Module):
@@ -47,6 +105,20 @@ class GPT2(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         """token ids (..., L) int64 -> logits (..., L, 50257) fp32 (gpt2.py:21-27)."""
         return _lm_forward(self, x, self.norm)
+
+    def hidden_rows(self, tokens: Tensor):
+        """(hidden rows (B, L, d) bf16, head weights (V, d) bf16): what forward's last GEMM and score's kernel both read."""
+        return _lm_hidden(self, tokens, self.norm)
+
+    @torch.no_grad()
+    def score(self, tokens: Tensor, lengths=None, *, return_argmax: bool = False):
+        """Teacher-forced scoring in O(B L) memory: tokens (B, L) int64 - exactly what forward takes - -> (B, L - 1) fp32 with
+        out[b, t] = log p(tokens[b, t + 1] | tokens[b, : t + 1]).  ``lengths`` (B,), 1 <= len_b <= L, marks a right-padded batch:
+        positions with t + 1 >= len_b are ignored and return 0, so out.sum(-1) is the sequence log-likelihood (and
+        -out.sum() / (lengths - 1).sum() the log-perplexity).  ``return_argmax``: also the (B, L - 1) int64 greedy predictions.
+        The vocabulary projection, the log-softmax and the gather are one kernel (ops.lm_score): the (B, L, 50257) logits are
+        never stored.  bf16 parameters on a HIP device."""
+        return _lm_score(self, tokens, self.norm, lengths, return_argmax, "GPT2.score")
 
     @torch.no_grad()
     def generate(self, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, topk: int = 1, seed: int = 0,

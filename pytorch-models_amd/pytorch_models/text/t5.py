@@ -167,9 +167,29 @@ class T5Model(nn.Module):
         return self.encoder(self._embed(x))
 
     def decode(self, x: Tensor, memory: Tensor) -> Tensor:
-        h = self.decoder(self._embed(x), memory)
-        W = _wb(self.classifier, "w", self.classifier.weight)
+        h, W = self.hidden_rows(x, memory)
         return ops.linear(h.reshape(-1, h.shape[-1]), W, None, out_dtype=torch.float32).view(*x.shape, W.shape[0])
+
+    def hidden_rows(self, x: Tensor, memory: Tensor):
+        """(hidden rows (..., L, d) bf16, classifier weights (V, d) bf16): what decode's last GEMM and score's kernel both read."""
+        h = self.decoder(self._embed(x), memory)
+        return h, _wb(self.classifier, "w", self.classifier.weight)
+
+    @torch.no_grad()
+    def score(self, x: Tensor, targets: Tensor, lengths=None, *, return_argmax: bool = False):
+        """Teacher-forced scoring in O(B L) memory: source ids x (B, S) and decoder input ids targets (B, L) int64 - exactly what
+        forward takes - -> (B, L - 1) fp32 with out[b, t] = log p(targets[b, t + 1] | targets[b, : t + 1], x[b]).  ``lengths``
+        (B,), 1 <= len_b <= L, marks right-padded decoder ids: positions with t + 1 >= len_b are ignored and return 0, so
+        out.sum(-1) is the sequence log-likelihood.  ``return_argmax``: also the (B, L - 1) int64 greedy predictions.  bf16
+        parameters on a HIP device; projection, log-softmax and gather are one kernel (ops.lm_score), the (B, L, vocab) logits
+        are never stored."""
+        from .gpt2 import score_gate, score_rows, score_targets
+
+        require_bf16_params(self, "T5Model.score")  # forward's own refusals (CPU model, fp32 parameters), in forward's order
+        score_gate("T5Model.score", self.classifier.weight, x, targets)
+        score_targets(targets, lengths, "T5Model.score")  # shape and lengths errors before any launch
+        h, W = self.hidden_rows(targets, self.encode(x))
+        return score_rows(h, W, targets, lengths, return_argmax, "T5Model.score")
 
     def forward(self, x: Tensor, targets: Tensor) -> Tensor:
         """token ids (..., S), (..., L) int64 -> logits (..., L, vocab) fp32 (t5.py:144-151)."""
