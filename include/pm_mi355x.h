@@ -293,6 +293,16 @@ int pm_dec_linear(const float* x, int64_t ldx, const float* gamma, const float* 
 /* Features per argmax tile of pm_dec_linear mode 2 for a given K (64, or 32 when K > 512). */
 int pm_dec_argmax_tile(int64_t K);
 
+/* Host-only query: the kernel instantiation and grid that pm_dec_linear (k_split = 0; mode 0, 1, 2), pm_dec_linear_ksplit (mode 0,
+ * k_split >= 2) or pm_dec_linear_kparts (mode 3, k_split >= 2) launches for these shapes, has_ln = gamma != NULL.  The launchers
+ * take their decision from the same function, PM_DEC_ROWSPLIT / PM_DEC_LOGITS_PERSIST / PM_DEC_LOGITS_WAVES included (the CU count
+ * is the current device's, 256 without one).  report: 10 int32 = kernel (0 dec_linear_kernel, 1 the persistent dec_logits_kernel),
+ * MT (16-row tiles per workgroup), FT (16-feature tiles per workgroup and inner step), NSTEP (K steps of 32 a wave holds in
+ * registers), LN, waves per workgroup, gridDim.x, gridDim.y (K parts), gridDim.z (row tiles on their own workgroups), the number of
+ * feature / arg-max tiles.  Returns the launcher's shape refusal (PM_EINVAL / PM_EUNSUPPORTED) where it has one.  Nothing is
+ * dereferenced or launched. */
+int pm_dec_linear_plan(int64_t M, int64_t N, int64_t K, int has_ln, int mode, int64_t k_split, int32_t* report);
+
 /* One query per (sequence, head), head_dim 64: out = softmax(q K^T / 8) V (transformer.py:52 with L_q = 1 and NO
  * causal flag - SURVEY.md F3).  q / out f32 (B, H*64); K/V bf16 addressed base + b*stride_b + h*stride_h + key*stride_k;
  * number of keys = (lk_ptr ? *lk_ptr : 0) + lk_add  (self: pos + 1; cross: the constant 1500), <= lk_max <= 4096. */

@@ -526,9 +526,13 @@ __global__ __launch_bounds__(256) void dec_linear_kernel(const float* __restrict
 // launch through the CUs' load paths, 26.9 us at Whisper-base).  Here a workgroup normalises x ONCE, keeps its three bf16
 // terms in registers and walks vocabulary tiles: 32 weight rows per inner step, the next step's rows requested before this
 // step's MFMAs, partial sums of the four waves (each owns every fourth K step, as in dec_linear_kernel) through a double-buffered
-// LDS area - one barrier per step, wave 0 reduces step s while everyone computes s + 1.  Every sum is formed in
-// dec_linear_kernel's order, so the logits and the (max, index) pairs are bit-identical to that kernel's.
-// NW waves share a row's K steps (wave w: steps w, w + NW, ...), NF 16-feature tiles per inner step.  <4, 2>: two 256-thread
+// LDS area - one barrier per step, wave 0 reduces step s while everyone computes s + 1.
+// NW waves share a row's K steps (wave w: steps w, w + NW, ...), NF 16-feature tiles per inner step.  Bit-identity with
+// dec_linear_kernel<.., ARGMAX> holds where the partition of K is that kernel's: in the <MT, 4, 2> form every sum (LayerNorm
+// statistics, MFMA chains, the waves' partial tiles) is formed in its order at every K, so the logits and the (max, index) pairs are
+// the same bits; the <MT, 8, 4> form gives wave w the steps w and w + 8 and adds eight partial tiles, which is the four-wave sum only
+// while waves 4 - 7 own no step (K <= 128: they add zeros) - beyond that its logits agree with the four-wave kernel's to rounding
+// (DESIGN.md 2g), not bit for bit.  tests/test_hip_decode_adversarial.py pins both statements.  <4, 2>: two 256-thread
 // workgroups per CU (round 2).  <8, 4> (round 3, the default): ONE 512-thread workgroup per CU - the x rows are loaded,
 // normalised and split once per CU instead of twice (stamps: 8.3 of the kernel's 20 us went by before its first MFMA, 128 KB of
 // x and ~2.3 us of VALU per CU), a step is a whole 64-feature arg-max tile.
@@ -1713,6 +1717,108 @@ extern "C" int pm_dec_embed_ragged(const int64_t* tok_cur, const void* emb, cons
   return dec_embed_impl<true>(tok_cur, emb, pos, pos_ptr, x, B, d, V, key_start, stream);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// THE launch decision of pm_dec_linear / pm_dec_linear_ksplit / pm_dec_linear_kparts: which kernel template, which instantiation
+// (MT row tiles, FT feature tiles, NSTEP K steps per wave in registers, LN), which grid.  The launchers below launch what this
+// returns and pm_dec_linear_plan reports it, so the two cannot drift apart.  Shapes only: pointers, leading dimensions and
+// alignment are the entry points' own checks.
+struct DlPlan {
+  int rc;                // PM_OK, or the refusal the launcher returns for these shapes
+  int kernel;            // 0 = dec_linear_kernel, 1 = dec_logits_kernel (persistent)
+  int mt, ft, nstep, ln; // template arguments (dec_logits_kernel: ft = NF, nstep = 16 / NW)
+  int nw;                // waves per workgroup
+  unsigned gx, gy, gz;   // grid
+  int nwg;               // feature (arg-max) tiles: the nwg / ntiles kernel argument
+  int halves;            // dec_logits_kernel: inner steps per arg-max tile
+};
+
+static int dl_mt_template(int mt) { return mt <= 1 ? 1 : (mt == 2 ? 2 : 4); }
+
+// NSTEP of dec_linear_kernel for `per_wave` K steps per wave, 0 = no instantiation serves it
+static int dl_nstep(bool ln, int ft, int mt, int per_wave) {
+  if (ln) {  // LayerNorm: the wave's whole share of x must sit in registers
+    if (mt > 2 && per_wave > 4) return 0;
+    if (per_wave <= 4) return 4;
+    if (per_wave <= 8 && ft == 1) return 8;
+    if (per_wave <= 10) return 10;
+    return 0;
+  }
+  return (per_wave <= 4 || mt > 2) ? 4 : 8;
+}
+
+static bool dl_rowsplit() {
+  static const bool on = [] { const char* e = getenv("PM_DEC_ROWSPLIT"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
+// k_split == 0: pm_dec_linear (modes 0, 1, 2); k_split >= 2: the K split (mode DL_PLAIN = pm_dec_linear_ksplit, DL_PARTS = _kparts)
+static DlPlan dl_plan(int64_t M, int64_t N, int64_t K, bool ln, int mode, int64_t k_split) {
+  DlPlan p = {PM_OK, 0, 1, 1, 4, ln ? 1 : 0, 4, 1, 1, 1, 0, 1};
+  if (M <= 0 || N <= 0 || K <= 0) { p.rc = PM_EINVAL; return p; }
+  if (M > 64 || K % 32) { p.rc = PM_EUNSUPPORTED; return p; }
+  int mt = (int)((M + 15) / 16);
+  if (k_split) {
+    if ((mode != DL_PLAIN && mode != DL_PARTS) || ln) { p.rc = PM_EINVAL; return p; }
+    if (k_split < 2 || k_split > 8 || K / 32 < k_split) { p.rc = PM_EINVAL; return p; }
+    p.nwg = (int)((N + DL_FEATS - 1) / DL_FEATS);
+    if (dl_rowsplit() && mt > 1 && p.nwg * mt * k_split <= 1024) { p.gz = (unsigned)mt; mt = 1; }
+    const int k_eff = (int)(((K / 32 + k_split - 1) / k_split) * 32);  // the longest part decides the instantiation
+    p.nstep = dl_nstep(false, 1, mt, (k_eff / 32 + 3) / 4);
+    p.mt = dl_mt_template(mt);
+    p.gx = (unsigned)p.nwg;
+    p.gy = (unsigned)k_split;
+    return p;
+  }
+  if (mode != DL_PLAIN && mode != DL_QKV && mode != DL_ARGMAX) { p.rc = PM_EINVAL; return p; }
+  if (K > 1280 && ln) { p.rc = PM_EUNSUPPORTED; return p; }
+  const int per_wave = (int)((K / 32 + 3) / 4);
+  p.ft = mode == DL_ARGMAX ? (ln && per_wave > 4 ? 2 : 4) : 1;  // see pm_dec_argmax_tile()
+  p.nwg = (int)((N + DL_FEATS * p.ft - 1) / (DL_FEATS * p.ft));
+  // rows are independent: with few feature tiles (N / 16 workgroups) the 16-row tiles go to separate workgroups, each
+  // reading only its rows of x (PM_DEC_ROWSPLIT=0 switches this off)
+  if (dl_rowsplit() && mode != DL_ARGMAX && mt > 1 && p.nwg * mt <= 512) { p.gz = (unsigned)mt; mt = 1; }
+  static const bool logits_persist = [] { const char* e = getenv("PM_DEC_LOGITS_PERSIST"); return !e || atoi(e) != 0; }();
+  if (mode == DL_ARGMAX && logits_persist && ln && M <= 32 && per_wave <= 4 && p.nwg >= 64) {
+    // final LayerNorm + vocabulary projection + arg-max tiles as one persistent launch (dec_logits_kernel); the arg-max tiles
+    // and their workspace layout are pm_dec_linear's (pm_dec_argmax_tile)
+    static const int cus = [] {
+      int dev = 0, n = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+      return n;
+    }();
+    // one 512-thread workgroup per CU whose step is a whole 64-feature tile (PM_DEC_LOGITS_WAVES=4: two 256-thread workgroups
+    // per CU, 32 features per step)
+    static const int lw = [] { const char* e = getenv("PM_DEC_LOGITS_WAVES"); return e ? atoi(e) : 8; }();
+    p.kernel = 1;
+    p.mt = mt <= 1 ? 1 : 2;
+    if (lw == 8 && p.ft == 4) {
+      p.nw = 8; p.ft = 4; p.nstep = 2; p.halves = 1;
+      p.gx = (unsigned)(p.nwg < cus ? p.nwg : cus);
+    } else {
+      p.nw = 4; p.halves = p.ft / 2; p.ft = 2; p.nstep = 4;
+      p.gx = (unsigned)(p.nwg < 2 * cus ? p.nwg : 2 * cus);
+    }
+    return p;
+  }
+  p.nstep = dl_nstep(ln, p.ft, mt, per_wave);
+  if (!p.nstep) { p.rc = PM_EUNSUPPORTED; return p; }
+  p.mt = dl_mt_template(mt);
+  p.gx = (unsigned)p.nwg;
+  return p;
+}
+
+/* Host-only: the instantiation and grid pm_dec_linear (k_split = 0; mode 0, 1, 2), pm_dec_linear_ksplit (mode 0, k_split >= 2) or
+ * pm_dec_linear_kparts (mode 3) would launch for these shapes; report = 10 int32: kernel (0 dec_linear_kernel, 1 the persistent
+ * dec_logits_kernel), MT, FT, NSTEP, LN, waves, gridDim.x, .y, .z, arg-max / feature tiles.  Nothing is dereferenced or launched. */
+extern "C" int pm_dec_linear_plan(int64_t M, int64_t N, int64_t K, int has_ln, int mode, int64_t k_split, int32_t* report) {
+  if (!report) return PM_EINVAL;
+  const DlPlan p = dl_plan(M, N, K, has_ln != 0, mode, k_split);
+  if (p.rc != PM_OK) return p.rc;
+  const int32_t r[10] = {p.kernel, p.mt, p.ft, p.nstep, p.ln, p.nw, (int32_t)p.gx, (int32_t)p.gy, (int32_t)p.gz, p.nwg};
+  for (int i = 0; i < 10; ++i) report[i] = r[i];
+  return PM_OK;
+}
+
 #define PM_DL_ARGS                                                                                                   \
   x, ldx, gamma, beta, eps, W, ldw, bias, resid, ldr, out, ldo, M, N, K, mode, kc, vc, inner, H, Tmax, pos_ptr, wv, wi, nwg
 template <int ACT, int FT, int NSTEP, bool LN>
@@ -1726,20 +1832,20 @@ static void dl_launch_mt(int mt, dim3 grid, hipStream_t st, const float* x, int 
 }
 
 template <int ACT, int FT>
-static int dl_launch(int mt, dim3 grid, hipStream_t st, const float* x, int ldx, const float* gamma, const float* beta,
+static int dl_launch(const DlPlan& p, hipStream_t st, const float* x, int ldx, const float* gamma, const float* beta,
                      float eps, const bf16* W, int64_t ldw, const float* bias, const float* resid, int ldr, float* out,
                      int ldo, int M, int N, int K, int mode, bf16* kc, bf16* vc, int inner, int H, int Tmax,
                      const int* pos_ptr, float* wv, int* wi, int nwg) {
-  const int per_wave = (K / 32 + 3) / 4;  // K steps each wave owns
-  if (gamma) {  // LayerNorm: the wave's whole share of x must sit in registers
-    if (mt > 2 && per_wave > 4) return PM_EUNSUPPORTED;
-    if (per_wave <= 4) dl_launch_mt<ACT, FT, 4, true>(mt, grid, st, PM_DL_ARGS);
-    else if (per_wave <= 8 && FT == 1) dl_launch_mt<ACT, FT, 8, true>(mt, grid, st, PM_DL_ARGS);
-    else if (per_wave <= 10 && FT == 1) dl_launch_mt<ACT, FT, 10, true>(mt, grid, st, PM_DL_ARGS);
-    else if (per_wave <= 10) dl_launch_mt<ACT, FT == 1 ? 1 : 2, 10, true>(mt, grid, st, PM_DL_ARGS);
+  const int mt = p.mt;
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if (p.ln) {
+    if (p.nstep == 4) dl_launch_mt<ACT, FT, 4, true>(mt, grid, st, PM_DL_ARGS);
+    else if (p.nstep == 8 && FT == 1) dl_launch_mt<ACT, FT, 8, true>(mt, grid, st, PM_DL_ARGS);
+    else if (p.nstep == 10 && FT == 1) dl_launch_mt<ACT, FT, 10, true>(mt, grid, st, PM_DL_ARGS);
+    else if (p.nstep == 10) dl_launch_mt<ACT, FT == 1 ? 1 : 2, 10, true>(mt, grid, st, PM_DL_ARGS);
     else return PM_EUNSUPPORTED;
   } else {
-    if (per_wave <= 4 || mt > 2) dl_launch_mt<ACT, FT, 4, false>(mt, grid, st, PM_DL_ARGS);
+    if (p.nstep == 4) dl_launch_mt<ACT, FT, 4, false>(mt, grid, st, PM_DL_ARGS);
     else dl_launch_mt<ACT, FT, 8, false>(mt, grid, st, PM_DL_ARGS);
   }
   return PM_OK;
@@ -1769,66 +1875,36 @@ extern "C" int pm_dec_linear(const float* x, int64_t ldx, const float* gamma, co
   }
   if (act != PM_ACT_NONE && act != PM_ACT_GELU && act != PM_ACT_GELU_TANH) return PM_EUNSUPPORTED;
   if (K > 1280 && gamma) return PM_EUNSUPPORTED;
-  const int per_wave = (int)((K / 32 + 3) / 4);
-  const int ft = mode == DL_ARGMAX ? (gamma && per_wave > 4 ? 2 : 4) : 1;  // see pm_dec_argmax_tile()
-  const int nwg = (int)((N + DL_FEATS * ft - 1) / (DL_FEATS * ft));
-  int mt = (int)((M + 15) / 16);
+  const DlPlan p = dl_plan(M, N, K, gamma != nullptr, mode, 0);
+  if (p.rc != PM_OK) return p.rc;
+  const int nwg = p.nwg;
   hipStream_t st = (hipStream_t)stream;
   int rc = PM_OK;
-  // rows are independent: with few feature tiles (N / 16 workgroups) the 16-row tiles go to separate workgroups, each
-  // reading only its rows of x (PM_DEC_ROWSPLIT=0 switches this off)
-  static const bool rowsplit = [] { const char* e = getenv("PM_DEC_ROWSPLIT"); return !e || atoi(e) != 0; }();
-  unsigned gz = 1;
-  if (rowsplit && mode != DL_ARGMAX && mt > 1 && nwg * mt <= 512) { gz = (unsigned)mt; mt = 1; }
-  static const bool logits_persist = [] { const char* e = getenv("PM_DEC_LOGITS_PERSIST"); return !e || atoi(e) != 0; }();
-  if (mode == DL_ARGMAX && logits_persist && gamma && M <= 32 && per_wave <= 4 && nwg >= 64) {
-    // final LayerNorm + vocabulary projection + arg-max tiles as one persistent launch (dec_logits_kernel); the arg-max tiles
-    // and their workspace layout are this function's (pm_dec_argmax_tile)
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      return n;
-    }();
-    // one 512-thread workgroup per CU whose step is a whole 64-feature tile (PM_DEC_LOGITS_WAVES=4: two 256-thread workgroups
-    // per CU, 32 features per step)
-    static const int lw = [] { const char* e = getenv("PM_DEC_LOGITS_WAVES"); return e ? atoi(e) : 8; }();
-    if (lw == 8 && ft == 4) {
-      const int grid = nwg < cus ? nwg : cus;
-      if (mt <= 1)
-        hipLaunchKernelGGL((dec_logits_kernel<1, 8, 4>), dim3(grid), dim3(512), 0, st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw,
-                           bias, (int)M, (int)N, (int)K, ws_val, (int*)ws_idx, nwg, 1);
-      else
-        hipLaunchKernelGGL((dec_logits_kernel<2, 8, 4>), dim3(grid), dim3(512), 0, st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw,
-                           bias, (int)M, (int)N, (int)K, ws_val, (int*)ws_idx, nwg, 1);
+#define PM_DL_CALL x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out, (int)ldo, (int)M, (int)N, (int)K, mode, \
+                   (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H, (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg
+#define PM_DLG(MT_, NW_, NF_)                                                                                                   \
+  hipLaunchKernelGGL((dec_logits_kernel<MT_, NW_, NF_>), dim3(p.gx), dim3(64 * NW_), 0, st, x, (int)ldx, gamma, beta, eps,        \
+                     (const bf16*)w, ldw, bias, (int)M, (int)N, (int)K, ws_val, (int*)ws_idx, nwg, p.halves)
+  if (p.kernel == 1) {
+    if (p.nw == 8) {
+      if (p.mt == 1) PM_DLG(1, 8, 4);
+      else PM_DLG(2, 8, 4);
     } else {
-      const int grid = nwg < 2 * cus ? nwg : 2 * cus;
-      if (mt <= 1)
-        hipLaunchKernelGGL((dec_logits_kernel<1, 4, 2>), dim3(grid), dim3(256), 0, st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw,
-                           bias, (int)M, (int)N, (int)K, ws_val, (int*)ws_idx, nwg, ft / 2);
-      else
-        hipLaunchKernelGGL((dec_logits_kernel<2, 4, 2>), dim3(grid), dim3(256), 0, st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw,
-                           bias, (int)M, (int)N, (int)K, ws_val, (int*)ws_idx, nwg, ft / 2);
+      if (p.mt == 1) PM_DLG(1, 4, 2);
+      else PM_DLG(2, 4, 2);
     }
-  } else if (mode == DL_ARGMAX && ft == 2)
-    rc = dl_launch<PM_ACT_NONE, 2>(mt, dim3(nwg), st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out,
-                              (int)ldo, (int)M, (int)N, (int)K, mode, (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H,
-                              (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg);
+  } else if (mode == DL_ARGMAX && p.ft == 2)
+    rc = dl_launch<PM_ACT_NONE, 2>(p, st, PM_DL_CALL);
   else if (mode == DL_ARGMAX)
-    rc = dl_launch<PM_ACT_NONE, 4>(mt, dim3(nwg), st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out,
-                              (int)ldo, (int)M, (int)N, (int)K, mode, (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H,
-                              (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg);
+    rc = dl_launch<PM_ACT_NONE, 4>(p, st, PM_DL_CALL);
   else if (act == PM_ACT_GELU_TANH)
-    rc = dl_launch<PM_ACT_GELU_TANH, 1>(mt, dim3(nwg, 1, gz), st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out,
-                           (int)ldo, (int)M, (int)N, (int)K, mode, (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H,
-                           (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg);
+    rc = dl_launch<PM_ACT_GELU_TANH, 1>(p, st, PM_DL_CALL);
   else if (act == PM_ACT_GELU)
-    rc = dl_launch<PM_ACT_GELU, 1>(mt, dim3(nwg, 1, gz), st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out,
-                           (int)ldo, (int)M, (int)N, (int)K, mode, (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H,
-                           (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg);
+    rc = dl_launch<PM_ACT_GELU, 1>(p, st, PM_DL_CALL);
   else
-    rc = dl_launch<PM_ACT_NONE, 1>(mt, dim3(nwg, 1, gz), st, x, (int)ldx, gamma, beta, eps, (const bf16*)w, ldw, bias, resid, (int)ldr, out,
-                           (int)ldo, (int)M, (int)N, (int)K, mode, (bf16*)kcache, (bf16*)vcache, (int)inner, (int)H,
-                           (int)Tmax, (const int*)pos_ptr, ws_val, (int*)ws_idx, nwg);
+    rc = dl_launch<PM_ACT_NONE, 1>(p, st, PM_DL_CALL);
+#undef PM_DLG
+#undef PM_DL_CALL
   if (rc != PM_OK) return rc;
   PM_CHECK_LAUNCH();
   return PM_OK;
@@ -1851,18 +1927,13 @@ static int dec_linear_ksplit_impl(const float* x, int64_t ldx, const void* w, in
   if (mode == DL_PARTS && ((((uintptr_t)out) & 15) || ldo % 4 || ldr % 4)) return PM_EALIGN;
   if (ldo < N || (mode == DL_PLAIN && resid && ldr < N)) return PM_EINVAL;
   if (act != PM_ACT_NONE && act != PM_ACT_GELU && act != PM_ACT_GELU_TANH) return PM_EUNSUPPORTED;
-  const int nwg = (int)((N + DL_FEATS - 1) / DL_FEATS);
-  int mt = (int)((M + 15) / 16);
-  static const bool rowsplit = [] { const char* e = getenv("PM_DEC_ROWSPLIT"); return !e || atoi(e) != 0; }();
-  unsigned gz = 1;
-  if (rowsplit && mt > 1 && nwg * mt * k_split <= 1024) { gz = (unsigned)mt; mt = 1; }
-  const int k_eff = (int)(((K / 32 + k_split - 1) / k_split) * 32);  // the longest part decides the instantiation
+  const DlPlan p = dl_plan(M, N, K, false, mode, k_split);
+  if (p.rc != PM_OK) return p.rc;
+  const int nwg = p.nwg, mt = p.mt;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(nwg, (unsigned)k_split, gz);
+  const dim3 grid(p.gx, p.gy, p.gz);
   int rc;
-  // (dl_launch picks NSTEP from its K argument; the kernel takes the true K from its own parameter list, so pass
-  // k_eff only for that choice: both instantiations below receive the real K)
-  const int per_wave = (k_eff / 32 + 3) / 4;
+  // (the plan picks NSTEP from the longest part; the kernel takes the true K from its own parameter list)
 #define PM_DLK(ACT_, NS_)                                                                                             \
   do {                                                                                                                \
     if (mt <= 1) hipLaunchKernelGGL((dec_linear_kernel<ACT_, 1, 1, NS_, false>), grid, dim3(256), 0, st, x, (int)ldx,   \
@@ -1881,13 +1952,13 @@ static int dec_linear_ksplit_impl(const float* x, int64_t ldx, const void* w, in
   } while (0)
   rc = PM_OK;
   if (act == PM_ACT_GELU) {
-    if (per_wave <= 4 || mt > 2) PM_DLK(PM_ACT_GELU, 4);
+    if (p.nstep == 4) PM_DLK(PM_ACT_GELU, 4);
     else PM_DLK(PM_ACT_GELU, 8);
   } else if (act == PM_ACT_GELU_TANH) {
-    if (per_wave <= 4 || mt > 2) PM_DLK(PM_ACT_GELU_TANH, 4);
+    if (p.nstep == 4) PM_DLK(PM_ACT_GELU_TANH, 4);
     else PM_DLK(PM_ACT_GELU_TANH, 8);
   } else {
-    if (per_wave <= 4 || mt > 2) PM_DLK(PM_ACT_NONE, 4);
+    if (p.nstep == 4) PM_DLK(PM_ACT_NONE, 4);
     else PM_DLK(PM_ACT_NONE, 8);
   }
 #undef PM_DLK

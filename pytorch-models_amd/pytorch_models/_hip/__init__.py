@@ -44,6 +44,7 @@ SIGNATURES = {
     "pm_mean_rows_bf16": ([_p, _p, _l, _l, _l, _p], c_int),
     "pm_dec_linear": ([_p, _l, _p, _p, _f, _p, _l, _p, _p, _l, _p, _l, _l, _l, _l, _i, _i, _p, _p, _l, _l, _l, _p, _p, _p, _p], c_int),
     "pm_dec_argmax_tile": ([_l], c_int),
+    "pm_dec_linear_plan": ([_l, _l, _l, _i, _i, _l, _p], c_int),
     "pm_dec_attention": ([_p, _p, _p, _l, _l, _l, _p, _l, _l, _p, _l, _l, _p], c_int),
     "pm_prefill_attention_bf16": ([_p, _l, _p, _p, _l, _l, _l, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
     "pm_dec_linear_ksplit": ([_p, _l, _p, _l, _p, _p, _l, _p, _l, _l, _l, _l, _i, _l, _p, _p, _p], c_int),

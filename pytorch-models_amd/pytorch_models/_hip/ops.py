@@ -3,6 +3,7 @@ current torch stream, raise on a non-zero status.  PyTorch is used for device me
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -702,6 +703,23 @@ def dec_argmax(x: Tensor, w: Tensor, ln: tuple) -> tuple[Tensor, Tensor]:
     best = wv.max(1)
     cand = torch.where(wv == best.values[:, None], wi, torch.full_like(wi, 2**31 - 1))
     return cand.min(1).values.long(), best.values
+
+
+DEC_LINEAR_PLAN_FIELDS = ("kernel", "MT", "FT", "NSTEP", "LN", "waves", "gx", "gy", "gz", "tiles")
+
+
+def dec_linear_plan(M: int, N: int, K: int, *, ln: bool = False, mode: int = 0, k_split: int = 0) -> dict:
+    """pm_dec_linear_plan: the instantiation and grid pm_dec_linear (k_split 0; mode 0 plain, 1 q/k/v, 2 arg-max tiles),
+    pm_dec_linear_ksplit (mode 0, k_split >= 2) or pm_dec_linear_kparts (mode 3) launches for these shapes - host only, the launchers
+    decide by the same function.  kernel: "linear" (dec_linear_kernel) or "logits" (the persistent dec_logits_kernel).  A shape the
+    launcher refuses comes back as {"refused": code}."""
+    rep = (ctypes.c_int32 * 10)()
+    rc = int(lib().pm_dec_linear_plan(M, N, K, int(bool(ln)), mode, k_split, ctypes.addressof(rep)))
+    if rc:
+        return {"refused": rc}
+    out = dict(zip(DEC_LINEAR_PLAN_FIELDS, (int(v) for v in rep)))
+    out["kernel"] = ("linear", "logits")[out["kernel"]]
+    return out
 
 
 def dec_attention(q: Tensor, k: Tensor, v: Tensor, lk: int) -> Tensor:

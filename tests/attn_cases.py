@@ -441,7 +441,7 @@ class DCase:
         return f"dec-{self.B}x{self.H}-T{self.T}-lk{self.lk}-{self.family}"
 
 
-DCASES = [DCase(4, 8, max(lk, 16) + (lk % 2) * 8, lk, fam) for lk in (1, 64, 65, 129, 1500) for fam in ("scale", "planted")]
+DCASES = [DCase(4, 8, max(lk, 16) + (lk % 2) * 8, lk, fam) for lk in (1, 64, 65, 129, 512, 513, 1024, 1025, 1500, 1537) for fam in ("scale", "planted")]
 
 
 def build_decode(c: DCase, per_batch_q: bool = True) -> dict:

@@ -51,3 +51,17 @@ def test_host_side_validation_launches_nothing():
     assert L.pm_linear_bf16(p, 65, p, 64, None, None, 0, 0, p, 8, 0, 4, 8, 64, 0, None) == 4
     assert L.pm_layernorm(p, 12, 0, p, p, 1e-5, p, 12, 0, 4, 12, None) == 2
     assert L.pm_vit_tokens(p, p, p, p, None, p, 1, 224, 224, 14, 384, None) == 2
+
+
+def test_dec_linear_plan_is_a_host_side_query():
+    """pm_dec_linear_plan dereferences nothing but its report and launches nothing: shapes in, the launchers' decision or refusal out."""
+    L = _hip.lib()
+    rep = (ctypes.c_int32 * 12)(*([-1] * 12))
+    p = ctypes.addressof(rep)
+    assert L.pm_dec_linear_plan(17, 130, 160, 0, 0, 0, None) == 1  # PM_EINVAL: no report
+    assert L.pm_dec_linear_plan(0, 130, 160, 0, 0, 0, p) == 1 and L.pm_dec_linear_plan(65, 130, 160, 0, 0, 0, p) == 2
+    assert L.pm_dec_linear_plan(17, 130, 1312, 1, 0, 0, p) == 2 and L.pm_dec_linear_plan(17, 130, 160, 0, 0, 9, p) == 1
+    assert list(rep) == [-1] * 12  # a refusal writes nothing
+    assert L.pm_dec_linear_plan(1, 16, 32, 0, 0, 0, p) == 0
+    assert list(rep) == [0, 1, 1, 4, 0, 4, 1, 1, 1, 1, -1, -1]  # dec_linear_kernel<., 1, 1, 4, false>, one workgroup; 10 fields, no more
+    assert L.pm_dec_linear_plan(1, 300, 1280, 1, 2, 0, p) == 0 and rep[2] * 16 == L.pm_dec_argmax_tile(1280)  # FT x 16 = the arg-max tile
