@@ -731,6 +731,39 @@ int pm_lm_score_bf16(const void* h, int64_t ldh, const void* w, int64_t ldw, con
                      int32_t* argmax, void* ws, int64_t M, int64_t V, int64_t K, void* stream);
 int64_t pm_lm_score_ws_bytes(int64_t M, int64_t V);
 
+/* ---- Whisper token timestamps (csrc/align.hip): cross-attention alignment matrix + dynamic time warping.  For B clips with
+ * len_b <= L token rows and F_b <= S frames, and the n_sel selected heads of ONE decoder layer (head dim 64):
+ *   lse[b, a, t] = log sum_{f < F_b} exp(q_t . k_f / 8);   p = exp(q_t . k_f / 8 - lse);   n = (p - mean_t p) / std_t p over t < len_b
+ *   (biased std; a column whose rows are all equal - std exactly 0 - gives 0);   m[b, t, f] (+)= inv_heads * sum_a median7_f(n[a, t, :]) with reflect
+ *   padding at 0 and F_b - 1.  The (n_sel, L, F) probabilities are never stored.
+ *   q bf16: row t of clip b = n_heads * 64 elements at q + b q_batch_stride + t ldq, head h at column 64 h; k likewise with S rows
+ *   (a view into a packed k|v projection has ldk = 2 * n_heads * 64).  Strides in elements, all % 8, bases 16-byte aligned (else
+ *   PM_EALIGN); ldq, ldk >= n_heads * 64 (else PM_EINVAL).  heads int32 (n_sel) device array of head indices (clamped into
+ *   [0, n_heads): a bad index cannot fault; callers validate); lengths, frames int32 (B) device arrays, 1 <= len_b <= L,
+ *   4 <= F_b <= S (clamped into [1, L] and [1, S] likewise).  B, n_sel <= 65535.
+ * pm_align_lse_bf16: lse f32 (B, n_sel, L) contiguous; rows t >= len_b are not written.  Any L.
+ * pm_align_matrix_bf16: one call per aligned layer, in a fixed order.  m f32: row t of clip b at m + b m_batch_stride + t ldm,
+ *   ldm >= S.  first != 0: m is overwritten, and entries with t >= len_b or f >= F_b are set to 0 (m needs no initial state);
+ *   first == 0: the call adds to the entries with t < len_b and f < F_b.  inv_heads = 1 / (heads of ALL calls).  L <= 448 (else
+ *   PM_EUNSUPPORTED).
+ * pm_align_dtw_f32: x = -m[b, skip_first : len_b - skip_last, 0 : F_b] (N rows, M columns), cost[0][0] = 0, the other border
+ *   cells +inf, cost[i][j] = x[i-1][j-1] + min(cost[i-1][j-1], cost[i-1][j], cost[i][j-1]) in fp32 with STRICT comparisons: the
+ *   diagonal if it is below both others, else the cell above if it is below both others, else the cell to the left; back from
+ *   (N, M) to (0, 0) in at most N + M moves whatever m holds.  start int32 (B, L) contiguous: the first frame of each row of the
+ *   window on that path, -1 for every other row (all rows when N <= 0).  ws: pm_align_ws_bytes(B, L, S) bytes (2 bits per cell in
+ *   8-byte words per row and 32 anti-diagonals), 8-byte aligned, no initial state.  L <= 448 (else PM_EUNSUPPORTED).
+ * No atomics: a clip's outputs are bit-identical wherever it sits in the batch and whatever B is. */
+int pm_align_lse_bf16(const void* q, int64_t ldq, int64_t q_batch_stride, const void* k, int64_t ldk, int64_t k_batch_stride,
+                      const int32_t* heads, const int32_t* lengths, const int32_t* frames, float* lse, int64_t B, int64_t L,
+                      int64_t S, int64_t n_sel, int64_t n_heads, void* stream);
+int pm_align_matrix_bf16(const void* q, int64_t ldq, int64_t q_batch_stride, const void* k, int64_t ldk, int64_t k_batch_stride,
+                         const int32_t* heads, const int32_t* lengths, const int32_t* frames, const float* lse, float* m,
+                         int64_t ldm, int64_t m_batch_stride, int64_t B, int64_t L, int64_t S, int64_t n_sel, int64_t n_heads,
+                         float inv_heads, int first, void* stream);
+int pm_align_dtw_f32(const float* m, int64_t ldm, int64_t m_batch_stride, const int32_t* lengths, const int32_t* frames,
+                     int32_t* start, void* ws, int64_t B, int64_t L, int64_t S, int64_t skip_first, int64_t skip_last, void* stream);
+int64_t pm_align_ws_bytes(int64_t B, int64_t L, int64_t S);
+
 #ifdef __cplusplus
 }
 #endif

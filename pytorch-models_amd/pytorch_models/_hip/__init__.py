@@ -121,6 +121,10 @@ SIGNATURES = {
     "pm_cls_head_gemm": ([_p, _l, _l, _p, _p, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
     "pm_lm_score_bf16": ([_p, _l, _p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p], c_int),
     "pm_lm_score_ws_bytes": ([_l, _l], c_int64),
+    "pm_align_lse_bf16": ([_p, _l, _l, _p, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_align_matrix_bf16": ([_p, _l, _l, _p, _l, _l, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _l, _f, _i, _p], c_int),
+    "pm_align_dtw_f32": ([_p, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_align_ws_bytes": ([_l, _l, _l], c_int64),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

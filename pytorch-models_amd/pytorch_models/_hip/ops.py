@@ -1598,3 +1598,102 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
     check(rc, f"pm_lm_score_bf16(M={M}, V={V}, K={K})")
     res = (out,) + ((lse,) if want_lse or lse_out is not None else ()) + ((am,) if want_argmax or argmax_out is not None else ())
     return res[0] if len(res) == 1 else res
+
+
+# ---- token timestamps (csrc/align.hip) ----
+ALIGN_MAX_ROWS = 448  # token rows one workgroup of pm_align_matrix_bf16 / pm_align_dtw_f32 holds
+
+
+def align_ws_bytes(B: int, L: int, S: int) -> int:
+    return int(lib().pm_align_ws_bytes(B, L, S))
+
+
+def align_counts(v, n: int, lo: int, hi: int, name: str, device) -> Tensor:
+    """Host ints (one int or a sequence of n) in [lo, hi] -> int32 (n) on ``device`` (one upload, before any launch); a device
+    int32 (n) tensor passes through unchecked (the kernels clamp what they read)."""
+    if isinstance(v, Tensor) and v.is_cuda:
+        _need(v.dtype == torch.int32 and v.shape == (n,) and v.is_contiguous(), f"{name} must be a contiguous int32 ({n},) tensor")
+        return v
+    vals = [int(v)] * n if isinstance(v, int) else [int(x) for x in (v.tolist() if isinstance(v, Tensor) else v)]
+    _need(len(vals) == n and all(lo <= x <= hi for x in vals), f"{name} must hold {n} values in [{lo}, {hi}], got {vals}")
+    return torch.tensor(vals, dtype=torch.int32).to(device)
+
+
+def _align_qk(who: str, q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tensor):
+    _cuda(q, k, heads, lengths, frames)
+    _need(q.dim() == 3 and k.dim() == 3 and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2],
+          f"{who}: q {tuple(q.shape)} vs k {tuple(k.shape)}")
+    _need(q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16, f"{who}: q and k must be bf16")
+    B, L, inner = q.shape
+    S = k.shape[1]
+    _need(B >= 1 and L >= 1 and S >= 4 and inner >= 64 and inner % 64 == 0, f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}: head dim 64 only")
+    _need(q.stride(2) == 1 and k.stride(2) == 1, f"{who}: q and k must have unit last strides")
+    _need(all(s % 8 == 0 for s in (q.stride(0), q.stride(1), k.stride(0), k.stride(1))), f"{who}: strides must be multiples of 8 elements")
+    for t, n, name in ((heads, None, "heads"), (lengths, B, "lengths"), (frames, B, "frames")):
+        _need(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.numel() >= 1 and (n is None or t.numel() == n),
+              f"{who}: {name} must be a contiguous int32 vector" + ("" if n is None else f" of {n}"))
+    return B, L, S, inner // 64, heads.numel()
+
+
+def align_lse(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tensor, out: Tensor | None = None) -> Tensor:
+    """pm_align_lse_bf16: q bf16 (B, L, H * 64), k bf16 (B, S, H * 64) (views with unit last stride; strides % 8), heads int32 (n)
+    head indices, lengths / frames int32 (B), all on the device -> lse f32 (B, n, L): log sum_{f < F_b} exp(q_t . k_f / 8) of each
+    selected head; rows t >= len_b are not written."""
+    B, L, S, H, nh = _align_qk("align_lse", q, k, heads, lengths, frames)
+    if out is None:
+        out = torch.empty((B, nh, L), dtype=torch.float32, device=q.device)
+    _need(out.dtype == torch.float32 and out.shape == (B, nh, L) and out.is_contiguous(), f"align_lse: out must be contiguous f32 {(B, nh, L)}")
+    rc = _launch("align_lse", (2.0 * B * nh * L * S * 64, float(2 * B * nh * (L + S) * 64)), lambda: lib().pm_align_lse_bf16(
+        q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), heads.data_ptr(), lengths.data_ptr(),
+        frames.data_ptr(), out.data_ptr(), B, L, S, nh, H, _stream()))
+    check(rc, f"pm_align_lse_bf16(B={B}, L={L}, S={S}, heads={nh})")
+    return out
+
+
+def align_matrix(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tensor, lse: Tensor, m: Tensor, inv_heads: float,
+                 first: bool) -> Tensor:
+    """pm_align_matrix_bf16: folds the selected heads of one layer (operands as align_lse, lse its result) into m f32 (B, L, S)
+    (unit last stride) with weight inv_heads: normalised over the tokens, median-filtered (7) along the frames.  ``first``
+    overwrites m and writes the zeros outside len_b / F_b; otherwise the call adds.  L <= 448."""
+    B, L, S, H, nh = _align_qk("align_matrix", q, k, heads, lengths, frames)
+    _cuda(q, lse, m)
+    _need(L <= ALIGN_MAX_ROWS, f"align_matrix: at most {ALIGN_MAX_ROWS} token rows, got {L}")
+    _need(lse.dtype == torch.float32 and lse.shape == (B, nh, L) and lse.is_contiguous(), f"align_matrix: lse must be contiguous f32 {(B, nh, L)}")
+    _need(m.dtype == torch.float32 and m.shape == (B, L, S) and m.stride(2) == 1 and m.stride(1) >= S,
+          f"align_matrix: m must be f32 {(B, L, S)} with a unit last stride")
+    rc = _launch("align_matrix", (2.0 * B * nh * L * S * 64, float(4 * B * L * S)), lambda: lib().pm_align_matrix_bf16(
+        q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), heads.data_ptr(), lengths.data_ptr(),
+        frames.data_ptr(), lse.data_ptr(), m.data_ptr(), m.stride(1), m.stride(0), B, L, S, nh, H, float(inv_heads), int(bool(first)),
+        _stream()))
+    check(rc, f"pm_align_matrix_bf16(B={B}, L={L}, S={S}, heads={nh})")
+    return m
+
+
+def align_dtw(m: Tensor, lengths, frames, skip_first: int = 0, skip_last: int = 0, *, out: Tensor | None = None,
+              ws: Tensor | None = None) -> Tensor:
+    """pm_align_dtw_f32: m f32 (B, L, S) (unit last stride), lengths / frames host ints (checked: 1 <= len_b <= L,
+    4 <= F_b <= S) or device int32 (B) -> start int32 (B, L): the first frame of each token row on the DTW path through
+    -m[b, skip_first : len_b - skip_last, : F_b] (fp32 additions and strict comparisons: the path is bit-determined), -1 outside
+    the window.  ``out`` / ``ws`` (uint8, align_ws_bytes(B, L, S)): caller-owned buffers.  L <= 448."""
+    _need(m.dim() == 3 and m.dtype == torch.float32 and m.stride(2) == 1, "align_dtw: m must be f32 (B, L, S) with a unit last stride")
+    B, L, S = m.shape
+    _need(B >= 1 and 1 <= L <= ALIGN_MAX_ROWS and S >= 4, f"align_dtw: m {tuple(m.shape)}: 1 <= L <= {ALIGN_MAX_ROWS}, S >= 4")
+    _need(m.stride(1) >= S, "align_dtw: rows of m overlap")
+    _need(isinstance(skip_first, int) and isinstance(skip_last, int) and skip_first >= 0 and skip_last >= 0,
+          f"align_dtw: skip_first / skip_last must be ints >= 0, got {skip_first!r}, {skip_last!r}")
+    lengths = align_counts(lengths, B, 1, L, "align_dtw: lengths", m.device)
+    frames = align_counts(frames, B, 4, S, "align_dtw: frames", m.device)
+    _cuda(m, lengths, frames, out, ws)
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.int32, device=m.device)
+    _need(out.dtype == torch.int32 and out.shape == (B, L) and out.is_contiguous(), f"align_dtw: out must be contiguous int32 {(B, L)}")
+    nws = align_ws_bytes(B, L, S)
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=m.device)
+    _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws and ws.data_ptr() % 8 == 0,
+          f"align_dtw: ws must hold {nws} bytes, 8-byte aligned")
+    rc = _launch("align_dtw", (float(B * L * S), float(4 * B * L * S + nws)), lambda: lib().pm_align_dtw_f32(
+        m.data_ptr(), m.stride(1), m.stride(0), lengths.data_ptr(), frames.data_ptr(), out.data_ptr(), ws.data_ptr(), B, L, S,
+        skip_first, skip_last, _stream()))
+    check(rc, f"pm_align_dtw_f32(B={B}, L={L}, S={S})")
+    return out

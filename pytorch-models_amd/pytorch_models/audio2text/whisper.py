@@ -143,6 +143,25 @@ class WhisperDecoder(nn.Module):
         return score_rows(h, E, tokens, lengths, return_argmax, "WhisperDecoder.score")
 
     @torch.no_grad()
+    def align(self, tokens: Tensor, memory: Tensor, *, lengths=None, frames=None, heads=None, skip_first: int = 0,
+              skip_last: int = 0, return_matrix: bool = False):
+        """Token timestamps by cross-attention alignment and dynamic time warping: tokens (B, L) int64 - the decoder's input ids,
+        as forward takes them - and memory (B, S, d) -> start (B, L) int32, the encoder position (Whisper.SECONDS_PER_FRAME each)
+        at which token t begins; a token ends where the next aligned one begins.  ``lengths`` / ``frames``: host ints or sequences
+        of B ints, 1 <= len_b <= L tokens and 4 <= F_b <= S encoder positions that count (defaults L and S).  ``heads``:
+        [(layer, head), ...], default every head of the upper half of the layers.  ``skip_first`` / ``skip_last``: rows dropped from
+        the warped window (the published use is skip_first = len(sot_sequence), skip_last = 1 with the eot row kept in tokens);
+        rows outside the window or at or beyond len_b return -1.  ``return_matrix``: also m (B, L, S) fp32, the normalised,
+        median-filtered, head-averaged attention the path runs through (exactly 0 where t >= len_b or f >= F_b).  A frame column
+        whose probabilities do not vary over the tokens (std exactly 0) normalises to 0, where the published code yields NaN.
+        bf16 parameters on a HIP device (audio2text/align.py, csrc/align.hip): no probabilities are stored and nothing waits for
+        the device; fp32 parameters raise NotImplementedError; a CPU module with CPU inputs takes the plain-torch form."""
+        from .align import align
+
+        return align(self, tokens, memory, lengths=lengths, frames=frames, heads=heads, skip_first=skip_first, skip_last=skip_last,
+                     return_matrix=return_matrix)
+
+    @torch.no_grad()
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
                  prefill: bool = False, lengths=None, pad_token_id: int = 0):
@@ -195,6 +214,14 @@ class Whisper(nn.Module):
         tokens[b, : t + 1] and the clip (WhisperDecoder.score's convention: ``lengths`` for a right-padded batch, ignored positions
         return 0, ``return_argmax`` adds the greedy predictions)."""
         return self.decoder.score(tokens, self.encoder(x), lengths, return_argmax=return_argmax)
+
+    SECONDS_PER_FRAME = 0.02  # one encoder position: two 10 ms mel frames
+
+    @torch.no_grad()
+    def align(self, x: Tensor, tokens: Tensor, **kwargs):
+        """log-mel (B, n_mels, T) + decoder input ids (B, L) -> start (B, L) int32 encoder positions (x SECONDS_PER_FRAME seconds):
+        WhisperDecoder.align on this clip's encoder output, with its keywords."""
+        return self.decoder.align(tokens, self.encoder(x), **kwargs)
 
     @torch.no_grad()
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",
