@@ -532,7 +532,9 @@ int pm_dwconv3_bn_act(const void* x, int x_dtype, const float* w, const float* s
                       float* psum, void* y, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C, int stride, void* stream);
 
 /* pm_se_gate: gate[n, :] = sigmoid(w2 @ silu(w1 @ m + b1) + b2) with m = (sum over t < ntiles of psum[n, t, :]) / hw
- * (SqueezeExcitation, maxvit.py:34-41).  psum f32 (N, ntiles, C); w1 f32 (R, C); w2 f32 (C, R); gate f32 (N, C).  fp32. */
+ * (SqueezeExcitation, maxvit.py:34-41).  psum f32 (N, ntiles, C); w1 f32 (R, C); w2 f32 (C, R); gate f32 (N, C).  fp32.
+ * C <= 16384, R <= 4096 and (C + R) * 4 <= 64 KiB (the pooled vector and the hidden one share one workgroup's LDS); anything
+ * beyond is PM_EUNSUPPORTED. */
 int pm_se_gate(const float* psum, int64_t ntiles, int64_t hw, const float* w1, const float* b1, const float* w2, const float* b2,
                float* gate, int64_t N, int64_t C, int64_t R, void* stream);
 
@@ -595,6 +597,11 @@ int pm_mixer_token_mix_bf16(const void* x, const float* stats, const float* gamm
                             const float* b1, const void* w2, const float* b2, void* y, float* row_out, int64_t N, int64_t T,
                             int64_t Dt, int64_t C, void* stream);
 int pm_mixer_token_mix_supported(int64_t T, int64_t Dt, int64_t C);
+/* pm_mixer_token_mix_plan: host only - what pm_mixer_token_mix_bf16 launches for (T, Dt, C), decided by the launcher's own
+ * functions.  report = 8 int32: NB (channels per workgroup / 32: 4 or 2), the dynamic LDS bytes, region_a (the byte offset of
+ * the hidden activations), nk1 = Tp / 16, nk2 = Dt / 16, nd = Dt / 32, nt = ceil(T / 32), and 1 where region_a is the per-wave
+ * scratch's size, 0 where it is the slab's.  PM_EUNSUPPORTED where pm_mixer_token_mix_supported is 0; a refusal writes nothing. */
+int pm_mixer_token_mix_plan(int64_t T, int64_t Dt, int64_t C, int32_t* report);
 
 /* pm_row_stats: stats[m] = (mean, rsqrt(biased variance + eps)) of row m of x (M, C), x_dtype rows with stride ldx: the format
  * pm_ln_stats_finalize writes, for rows that no GEMM epilogue has summed.  fp32, centred second pass. */

@@ -486,8 +486,9 @@ extern "C" int pm_se_gate(const float* psum, int64_t ntiles, int64_t hw, const f
                           const float* b2, float* gate, int64_t N, int64_t C, int64_t R, void* stream) {
   if (!psum || !w1 || !b1 || !w2 || !b2 || !gate || N < 0 || ntiles <= 0 || hw <= 0 || C <= 0 || R <= 0) return PM_EINVAL;
   if (C > 16384 || R > 4096 || ntiles > (1 << 20) || N > 0x7fffffff) return PM_EUNSUPPORTED;
-  if (N == 0) return PM_OK;
   const size_t lds = (size_t)(C + R) * sizeof(float);
+  if (lds > 64 * 1024) return PM_EUNSUPPORTED;  // the default dynamic-LDS limit, which this kernel never raises
+  if (N == 0) return PM_OK;
   hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)N), dim3(256), lds, (hipStream_t)stream, psum, (int)ntiles,
                      1.0f / (float)hw, w1, b1, w2, b2, gate, (int)C, (int)R);
   PM_CHECK_LAUNCH();

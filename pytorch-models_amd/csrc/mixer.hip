@@ -343,6 +343,20 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int pm_mixer_token_mix_supported(int64_t T, int64_t Dt, int64_t C) { return mx_pick_nb(T, Dt, C) ? 1 : 0; }
 
+/* Host-only: what pm_mixer_token_mix_bf16 launches for these shapes, from the functions it launches by; report = 8 int32: NB,
+ * the dynamic LDS bytes, region_a, nk1, nk2, nd, nt, and 1 where region_a is the per-wave scratch (the slab is smaller), 0 where
+ * it is the slab.  Nothing is dereferenced but the report, nothing is launched; a refusal writes nothing. */
+extern "C" int pm_mixer_token_mix_plan(int64_t T, int64_t Dt, int64_t C, int32_t* report) {
+  if (!report) return PM_EINVAL;
+  const int nb = mx_pick_nb(T, Dt, C);
+  if (!nb) return PM_EUNSUPPORTED;
+  const int ra = mx_region_a(nb, (int)T);
+  const int32_t r[8] = {nb, mx_lds_bytes(nb, (int)T, (int)Dt), ra, mx_tp((int)T) / 16, (int32_t)(Dt / 16), (int32_t)(Dt / 32),
+                        (int32_t)((T + 31) / 32), 32 * nb * (mx_tp((int)T) + 8) * 2 > MX_SCR_BYTES ? 0 : 1};
+  for (int i = 0; i < 8; ++i) report[i] = r[i];
+  return PM_OK;
+}
+
 extern "C" int pm_mixer_token_mix_bf16(const void* x, const float* stats, const float* gamma, const float* beta, const void* w1,
                                        const float* b1, const void* w2, const float* b2, void* y, float* row_out, int64_t N,
                                        int64_t T, int64_t Dt, int64_t C, void* stream) {

@@ -96,6 +96,7 @@ SIGNATURES = {
     "pm_attention_hd32_bf16": ([_p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
     "pm_mixer_token_mix_bf16": ([_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _p], c_int),
     "pm_mixer_token_mix_supported": ([_l, _l, _l], c_int),
+    "pm_mixer_token_mix_plan": ([_l, _l, _l, _p], c_int),
     "pm_row_stats": ([_p, _l, _i, _p, _l, _l, _f, _p], c_int),
     "pm_ln_mean": ([_p, _i, _p, _p, _p, _p, _i, _l, _l, _l, _p], c_int),
     "pm_transpose_add_f32": ([_p, _p, _p, _l, _l, _l, _l, _p], c_int),

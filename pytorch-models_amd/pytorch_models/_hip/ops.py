@@ -1270,6 +1270,22 @@ def mixer_token_mix_supported(T: int, Dt: int, C: int) -> bool:
     return bool(lib().pm_mixer_token_mix_supported(T, Dt, C))
 
 
+MIXER_TOKEN_MIX_PLAN_FIELDS = ("NB", "lds", "region_a", "nk1", "nk2", "nd", "nt", "scratch")
+
+
+def mixer_token_mix_plan(T: int, Dt: int, C: int) -> dict:
+    """pm_mixer_token_mix_plan: the slab width (NB x 32 channels), LDS layout and strip counts pm_mixer_token_mix_bf16 launches
+    with for these shapes - host only, the launcher decides by the same functions.  scratch: region_a is the per-wave scratch's
+    size (True) or the slab's (False).  A shape the launcher refuses comes back as {"refused": code}."""
+    rep = (ctypes.c_int32 * 8)()
+    rc = int(lib().pm_mixer_token_mix_plan(T, Dt, C, ctypes.addressof(rep)))
+    if rc:
+        return {"refused": rc}
+    out = dict(zip(MIXER_TOKEN_MIX_PLAN_FIELDS, (int(v) for v in rep)))
+    out["scratch"] = bool(out["scratch"])
+    return out
+
+
 def mixer_pack_weight(w: Tensor) -> Tensor:
     """An nn.Linear weight (R, K) -> bf16 [ceil(R/32)][ceil(K/16)][64][8], the fragment-major, zero-padded form
     pm_mixer_token_mix_bf16 reads (include/pm_mi355x.h): lane l of strip s, step k holds w[32 s + (l & 31)][16 k + 8 (l >> 5) + 0..7]."""

@@ -65,3 +65,19 @@ def test_dec_linear_plan_is_a_host_side_query():
     assert L.pm_dec_linear_plan(1, 16, 32, 0, 0, 0, p) == 0
     assert list(rep) == [0, 1, 1, 4, 0, 4, 1, 1, 1, 1, -1, -1]  # dec_linear_kernel<., 1, 1, 4, false>, one workgroup; 10 fields, no more
     assert L.pm_dec_linear_plan(1, 300, 1280, 1, 2, 0, p) == 0 and rep[2] * 16 == L.pm_dec_argmax_tile(1280)  # FT x 16 = the arg-max tile
+
+
+def test_mixer_token_mix_plan_is_a_host_side_query():
+    """pm_mixer_token_mix_plan dereferences nothing but its report and launches nothing, and agrees with pm_mixer_token_mix_supported."""
+    L = _hip.lib()
+    rep = (ctypes.c_int32 * 10)(*([-1] * 10))
+    p = ctypes.addressof(rep)
+    assert L.pm_mixer_token_mix_plan(16, 32, 64, None) == 1  # PM_EINVAL: no report
+    for T, Dt, C in ((0, 32, 64), (16, 48, 64), (16, 32, 96), (16, 1024, 128), (4097, 32, 64)):
+        assert L.pm_mixer_token_mix_plan(T, Dt, C, p) == 2 and not L.pm_mixer_token_mix_supported(T, Dt, C), (T, Dt, C)
+    assert list(rep) == [-1] * 10  # a refusal writes nothing
+    assert L.pm_mixer_token_mix_plan(196, 384, 768, p) == 0 and L.pm_mixer_token_mix_supported(196, 384, 768)
+    # NB 4: the slab 128 x (208 + 8) x 2 B is region_a, + 128 x (384 + 8) x 2 B of hidden activations; 8 fields, no more
+    assert list(rep) == [4, 55296 + 100352, 55296, 13, 24, 12, 7, 0, -1, -1]
+    assert L.pm_mixer_token_mix_plan(1, 32, 64, p) == 0
+    assert list(rep)[:8] == [2, 33792 + 64 * 40 * 2, 33792, 1, 2, 1, 1, 1]  # NB 2 (C % 128), region_a = 8 waves x 32 x 33 x 4 B of scratch
