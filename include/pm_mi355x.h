@@ -771,6 +771,48 @@ int pm_align_dtw_f32(const float* m, int64_t ldm, int64_t m_batch_stride, const 
                      int32_t* start, void* ws, int64_t B, int64_t L, int64_t S, int64_t skip_first, int64_t skip_last, void* stream);
 int64_t pm_align_ws_bytes(int64_t B, int64_t L, int64_t S);
 
+/* ---- Variable-length (packed) encoder batches (csrc/varlen.hip, csrc/attention_bf16.hip; DESIGN.md "packed sequences").
+ * B right-padded sequences run as one (T_total, d) matrix, T_total = sum(len_b).  cu_seqlens: int32 (B + 1) in DEVICE memory,
+ * cu[0] = 0, non-decreasing; sequence b owns rows cu[b] .. cu[b + 1].  The caller guarantees that the packed operand holds
+ * cu[B] rows; the padded side is protected by clamping len_b to [0, L].  Strides are in elements. */
+
+/* Self-attention of every sequence with itself, head_dim 64, bf16: for rows i, j of sequence b,
+ * o[cu[b] + i, h, :] = softmax_j(q[cu[b] + i, h, :] . k[cu[b] + j, h, :] / 8 [j <= i if causal]) v[cu[b] + j, h, :].
+ * q / k / v / o: packed rows addressed base + row*stride_t + h*64 (column slices of one packed QKV projection are consumed in
+ * place).  The tiled kernel of pm_attention_bf16 with per-sequence extents: the grid is B * H * ceil(max_len / 128) workgroups
+ * (max_len >= every len_b; it sizes the grid and nothing else), a workgroup whose query block lies past its sequence returns
+ * at once, and key tiles come from the sequence's own length.  A sequence of length 0 writes nothing; rows outside
+ * 0 .. cu[B] are neither read nor written.  Per sequence the arithmetic is that of pm_attention_bf16's tiled kernel on that
+ * sequence alone, whatever its position in the batch.  No bias, no cross-attention. */
+int pm_attention_varlen_bf16(const void* q, int64_t q_stride_t, const void* k, int64_t k_stride_t, const void* v,
+                             int64_t v_stride_t, void* o, int64_t o_stride_t, const int32_t* cu_seqlens, int64_t B,
+                             int64_t H, int64_t max_len, int causal, void* stream);
+
+/* pm_embed_tokens into packed rows: out[cu[b] + t, :] = emb[tokens[b, t], :] + pos[t, :] for t < len_b.  tokens: int64 (B, L)
+ * contiguous, right-padded (ids at t >= len_b are not read); emb: (V, d) of emb_dtype (PM_BF16 | PM_F32; an f32 table needs
+ * out_dtype PM_F32); pos: f32 (>= L, d) or NULL; out: (cu[B], d) contiguous.  Ids are clamped to [0, V) like pm_embed_tokens. */
+int pm_embed_tokens_varlen(const int64_t* tokens, const void* emb, int emb_dtype, const float* pos,
+                           const int32_t* cu_seqlens, void* out, int out_dtype, int64_t B, int64_t L, int64_t d,
+                           int64_t V, void* stream);
+
+/* Plain row copies between the padded (B, L, d) layout (x_stride_b / x_stride_t, unit last stride) and the packed (cu[B], d)
+ * layout, 16-byte accesses: d * elem_bytes and every stride in bytes must be multiples of 16, elem_bytes is 2 or 4.
+ *   pm_rows_pack:      out[cu[b] + t] = x[b, t]                       for t < len_b (padded rows are not read)
+ *   pm_rows_unpack:    out[b, t] = t < len_b ? x[cu[b] + t] : 0       for every t < L
+ *   pm_rows_zero_tail: x[b, t] = 0                                    for len_b <= t < L, in place */
+int pm_rows_pack(const void* x, int64_t x_stride_b, int64_t x_stride_t, const int32_t* cu_seqlens, void* out,
+                 int64_t out_stride_t, int64_t B, int64_t L, int64_t d, int64_t elem_bytes, void* stream);
+int pm_rows_unpack(const void* x, int64_t x_stride_t, const int32_t* cu_seqlens, void* out, int64_t out_stride_b,
+                   int64_t out_stride_t, int64_t B, int64_t L, int64_t d, int64_t elem_bytes, void* stream);
+int pm_rows_zero_tail(void* x, int64_t x_stride_b, int64_t x_stride_t, const int32_t* cu_seqlens, int64_t B, int64_t L,
+                      int64_t d, int64_t elem_bytes, void* stream);
+
+/* out[b, :] = mean of the rows cu[b] .. cu[b + 1] of x (packed, x_dtype PM_BF16 | PM_F32, row stride x_stride_t) -> f32 (B, d)
+ * contiguous.  fp32 accumulation over the rows in order, one divide: the result is bit-determined (no atomics).  A sequence of
+ * length 0 gives zeros.  d % 8 == 0 (bf16) / % 4 (f32); B <= 65535. */
+int pm_segment_mean(const void* x, int64_t x_stride_t, int x_dtype, const int32_t* cu_seqlens, float* out, int64_t B,
+                    int64_t d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,13 +40,19 @@ __device__ __forceinline__ bf16x8 tr_read_pair(const char* p0, const char* p1) {
   return u.v;
 }
 
-template <bool CAUSAL, bool BIAS>
+// VARLEN (pm_attention_varlen_bf16): the operands are packed (T_total, H*64) rows, sequence b owns rows cu[b] .. cu[b + 1] and
+// attends to itself only: Lq = Lk = its own length (the arguments carry max_len, which only sizes the grid), the batch strides
+// are not read.  A workgroup whose query block starts at or past its sequence's end returns here - a function of blockIdx alone,
+// in front of every barrier -, and nT below comes from the sequence's own length, so padded key tiles never exist.  Everything
+// behind this prologue is the one tile body: the other instantiations compile to the code they had.
+template <bool CAUSAL, bool BIAS, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_hd64(const bf16* __restrict__ Q, int64_t qsb, int64_t qst,
                                                      const bf16* __restrict__ K, int64_t ksb, int64_t kst,
                                                      const bf16* __restrict__ V, int64_t vsb, int64_t vst,
-                                                     bf16* __restrict__ O, int64_t osb, int64_t ost, int H, int Lq,
-                                                     int Lk, int nqb, const float* __restrict__ bias, int64_t bsb,
-                                                     int64_t bsh, int64_t bsq) {
+                                                     bf16* __restrict__ O, int64_t osb, int64_t ost, int H, int Lq_arg,
+                                                     int Lk_arg, int nqb, const float* __restrict__ bias, int64_t bsb,
+                                                     int64_t bsh, int64_t bsq, const int* __restrict__ cu) {
+  static_assert(!(VARLEN && BIAS), "the variable-length form takes no bias");
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];  // [buf][K, V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -56,9 +62,17 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64(const bf16* __restrict__ Q,
   const int q0 = qb * 128;
   const int r = lane & 31, hh = lane >> 5;
 
-  const bf16* Qp = Q + (int64_t)b * qsb + h * 64;
-  const bf16* Kp = K + (int64_t)b * ksb + h * 64;
-  const bf16* Vp = V + (int64_t)b * vsb + h * 64;
+  int Lq = Lq_arg, Lk = Lk_arg;
+  if constexpr (VARLEN) {
+    const int row0 = cu[b];
+    Lq = Lk = cu[b + 1] - row0;
+    if (q0 >= Lq) return;  // also every workgroup of a sequence of length 0
+    qsb = (int64_t)row0 * qst; ksb = (int64_t)row0 * kst; vsb = (int64_t)row0 * vst; osb = (int64_t)row0 * ost;
+  }
+  const int64_t bo = VARLEN ? 1 : b;  // (VARLEN: the "batch stride" above is the sequence's first row)
+  const bf16* Qp = Q + bo * qsb + h * 64;
+  const bf16* Kp = K + bo * ksb + h * 64;
+  const bf16* Vp = V + bo * vsb + h * 64;
 
   // this lane's query row (clamped for loads; masked at the store)
   const int qi = q0 + wave * 32 + r;
@@ -252,7 +266,7 @@ _Pragma("unroll")                                                               
   const float l_tot = ah_add_xor32(l_run);
   const float inv = BIAS ? (l_tot > 0.f ? 1.0f / l_tot : 0.f) : 1.0f / l_tot;
   if (qi < Lq) {
-    bf16* op = O + (int64_t)b * osb + (int64_t)qi * ost + h * 64;
+    bf16* op = O + bo * osb + (int64_t)qi * ost + h * 64;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -722,7 +736,7 @@ static int attention_impl(const void* q, int64_t q_stride_b, int64_t q_stride_t,
 #define PM_ATT(C_, B_)                                                                                                   \
   hipLaunchKernelGGL((attn_fwd_hd64<C_, B_>), dim3((unsigned)nblk), dim3(256), 0, st, (const bf16*)q, q_stride_b, q_stride_t, \
                      (const bf16*)k, k_stride_b, k_stride_t, (const bf16*)v, v_stride_b, v_stride_t, (bf16*)o, o_stride_b,  \
-                     o_stride_t, (int)H, (int)Lq, (int)Lk, nqb, bias, bsb, bsh, bsq)
+                     o_stride_t, (int)H, (int)Lq, (int)Lk, nqb, bias, bsb, bsh, bsq, (const int*)nullptr)
   static const bool short_ok = [] { const char* e = getenv("PM_ATTN_SHORT"); return !e || atoi(e) != 0; }();
   if (short_ok && !causal && !bias && Lk <= 256 && Lq <= 256 && !((o_stride_t | o_stride_b) % 8) && !((uintptr_t)o & 15)) {
     // short self-attention: one persistent workgroup per CU walks the heads (K / V of a head in LDS once, one-pass softmax)
@@ -778,4 +792,34 @@ extern "C" int pm_attention_bias_bf16(const void* q, int64_t q_stride_b, int64_t
   if (!bias) return PM_EINVAL;
   return attention_impl(q, q_stride_b, q_stride_t, k, k_stride_b, k_stride_t, v, v_stride_b, v_stride_t, o, o_stride_b,
                         o_stride_t, B, H, Lq, Lk, causal, bias, bias_stride_b, bias_stride_h, bias_stride_q, stream);
+}
+
+/* The tiled kernel over a packed batch: see include/pm_mi355x.h.  The grid is sized by max_len; the sequences' own extents come
+ * from cu_seqlens on the device (attn_fwd_hd64<., false, true>). */
+extern "C" int pm_attention_varlen_bf16(const void* q, int64_t q_stride_t, const void* k, int64_t k_stride_t, const void* v,
+                                        int64_t v_stride_t, void* o, int64_t o_stride_t, const int32_t* cu_seqlens, int64_t B,
+                                        int64_t H, int64_t max_len, int causal, void* stream) {
+  if (!q || !k || !v || !o || !cu_seqlens || B < 0 || H <= 0 || max_len <= 0) return PM_EINVAL;
+  if ((q_stride_t | k_stride_t | v_stride_t) % 8) return PM_EALIGN;
+  if (o_stride_t % 4) return PM_EALIGN;
+  if (q_stride_t < H * 64 || k_stride_t < H * 64 || v_stride_t < H * 64 || o_stride_t < H * 64) return PM_EINVAL;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return PM_EALIGN;
+  if ((uintptr_t)o & 7) return PM_EALIGN;
+  if ((uintptr_t)cu_seqlens & 3) return PM_EALIGN;
+  if (max_len > (1 << 24)) return PM_EINVAL;
+  if (B == 0) return PM_OK;
+  const int nqb = (int)((max_len + 127) / 128);
+  const int64_t nblk = B * H * nqb;
+  if (nblk > 0x7fffffff) return PM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+#define PM_ATTV(C_)                                                                                                      \
+  hipLaunchKernelGGL((attn_fwd_hd64<C_, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, (const bf16*)q, (int64_t)0,  \
+                     q_stride_t, (const bf16*)k, (int64_t)0, k_stride_t, (const bf16*)v, (int64_t)0, v_stride_t, (bf16*)o,  \
+                     (int64_t)0, o_stride_t, (int)H, (int)max_len, (int)max_len, nqb, (const float*)nullptr, (int64_t)0,    \
+                     (int64_t)0, (int64_t)0, (const int*)cu_seqlens)
+  if (causal) PM_ATTV(true);
+  else PM_ATTV(false);
+#undef PM_ATTV
+  PM_CHECK_LAUNCH();
+  return PM_OK;
 }

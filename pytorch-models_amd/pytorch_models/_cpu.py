@@ -52,6 +52,18 @@ def mha(m, q: Tensor, k, v, attn_bias, causal: bool, residual: Tensor | None) ->
     return y if residual is None else residual.to(dt) + y
 
 
+def mha_packed(m, x: Tensor, seq, causal: bool, residual: Tensor | None) -> Tensor:
+    """MHA.attend_packed on the CPU: `mha` on each sequence's rows cu[b] .. cu[b + 1] of the packed (T_total, d) input."""
+    dt = m.q_proj.weight.dtype
+    out, r0 = [], 0
+    for n in seq.lengths:
+        if n:
+            out.append(mha(m, x[r0 : r0 + n][None], None, None, None, causal, None)[0])
+        r0 += n
+    y = torch.cat(out, 0) if out else x.new_zeros((0, m.out_proj.out_features), dtype=dt)
+    return y if residual is None else residual.to(dt) + y
+
+
 def mlp(m, x: Tensor, residual: Tensor | None) -> Tensor:
     """reference transformer.py:56-67."""
     dt = m.linear1.weight.dtype
@@ -102,3 +114,54 @@ def whisper_log_mel(x: Tensor, window: Tensor, filters: Tensor) -> Tensor:
     y = y.clamp(0).log10()
     y = y.maximum(y.flatten(-2).max(-1, keepdim=True)[0].unsqueeze(-1) - 8)
     return (y + 4) / 4
+
+
+# ---- variable-length batches (lengths=): the packed layout of the HIP path in plain torch
+def rows_pack(x: Tensor, lengths) -> Tensor:
+    """padded (B, L, ...) -> packed (sum(lengths), ...): the first lengths[b] rows of every sample, in order."""
+    return torch.cat([x[b, :n] for b, n in enumerate(lengths)], 0)
+
+
+def rows_unpack(x: Tensor, lengths, L: int) -> Tensor:
+    """packed (sum(lengths), d) -> padded (B, L, d), zeros past each length."""
+    out = x.new_zeros((len(lengths), L, x.shape[-1]))
+    r0 = 0
+    for b, n in enumerate(lengths):
+        out[b, :n] = x[r0 : r0 + n]
+        r0 += n
+    return out
+
+
+def segment_mean(x: Tensor, lengths) -> Tensor:
+    """packed (sum(lengths), d) -> fp32 (B, d): the mean of each sequence's rows (zeros for a length of 0)."""
+    out = torch.zeros((len(lengths), x.shape[-1]), dtype=torch.float32)
+    r0 = 0
+    for b, n in enumerate(lengths):
+        if n:
+            out[b] = x[r0 : r0 + n].float().mean(0)
+        r0 += n
+    return out
+
+
+def w2v_features(m, x: Tensor) -> Tensor:
+    """reference audio/wav2vec2.py:19-39, 66-68 for the layer-norm stem: conv -> LayerNorm over channels -> GELU per stem layer,
+    then the LayerNorm [+ Linear] projection; waveform (B, n) -> (B, T, d).  Serves Wav2Vec2.forward(x, lengths=) on the CPU."""
+    dt = m.proj[0].weight.dtype
+    h = x.to(dt)[:, None, :]
+    for blk in m.feature_encoder:
+        conv, norm = blk[0], blk[2]
+        h = F.conv1d(h, conv.weight, conv.bias, conv.stride)
+        h = F.layer_norm(h.transpose(1, 2), norm.normalized_shape, norm.weight, norm.bias, norm.eps).transpose(1, 2)
+        h = F.gelu(h)
+    h = h.transpose(1, 2)
+    for layer in m.proj:
+        h = layer(h)
+    return h
+
+
+def w2v_positional(m, h: Tensor) -> Tensor:
+    """reference audio/wav2vec2.py:80: x + GELU(grouped conv(pad(x))) on time-major (B, T, d)."""
+    conv = m.pe_conv[1]
+    pad = m.pe_conv[0].padding
+    y = F.conv1d(F.pad(h.transpose(1, 2), (pad[0], pad[1])), conv.weight, conv.bias, conv.stride, groups=conv.groups)
+    return h + F.gelu(y).transpose(1, 2)

@@ -1713,3 +1713,150 @@ def align_dtw(m: Tensor, lengths, frames, skip_first: int = 0, skip_last: int = 
         skip_first, skip_last, _stream()))
     check(rc, f"pm_align_dtw_f32(B={B}, L={L}, S={S})")
     return out
+
+
+# ---- variable-length (packed) encoder batches: csrc/varlen.hip and pm_attention_varlen_bf16 ("packed sequences") ----
+class SeqLens:
+    """The extents of a right-padded batch, built once per forward by ``seq_lens``: ``lengths`` (host ints, B of them),
+    ``cu`` (int32 (B + 1) cumulative row offsets on the device, cu[0] = 0), ``total`` = sum(lengths), ``max_len``, ``B``, ``L``."""
+    __slots__ = ("lengths", "cu", "total", "max_len", "B", "L")
+
+    def __init__(self, lengths: list[int], cu: Tensor, L: int) -> None:
+        self.lengths, self.cu, self.L = lengths, cu, L
+        self.B, self.total, self.max_len = len(lengths), sum(lengths), max(lengths, default=0)
+
+
+def seq_lens(lengths, L: int, device, lo: int = 0) -> SeqLens:
+    """lengths: B host ints, or a 1-D integer tensor (read back once), each in [lo, L] -> SeqLens with cu_seqlens on ``device``
+    (one upload, in front of every launch).  Validated on the host: the kernels trust cu_seqlens."""
+    if isinstance(lengths, Tensor):
+        _need(lengths.dim() == 1 and not lengths.dtype.is_floating_point and lengths.dtype != torch.bool,
+              f"lengths must be a 1-D integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
+        vals = [int(v) for v in lengths.tolist()]
+    else:
+        vals = list(lengths)
+        _need(all(isinstance(v, int) and not isinstance(v, bool) for v in vals), f"lengths must be ints, got {vals}")
+    _need(all(lo <= v <= L for v in vals), f"lengths must lie in [{lo}, {L}], got {vals}")
+    cu = [0]
+    for v in vals:
+        cu.append(cu[-1] + v)
+    _need(cu[-1] < 2 ** 31, "lengths: more than 2^31 rows")
+    return SeqLens(vals, torch.tensor(cu, dtype=torch.int32).to(device), int(L))
+
+
+def _seq(seq: SeqLens, what: str, *ts: Tensor) -> None:
+    _need(isinstance(seq, SeqLens) and seq.cu.dtype == torch.int32 and seq.cu.shape == (seq.B + 1,) and seq.cu.is_contiguous(),
+          f"{what}: seq must come from ops.seq_lens")
+    _cuda(seq.cu, *ts)
+
+
+def attention_varlen(q: Tensor, k: Tensor, v: Tensor, n_heads: int, seq: SeqLens, causal: bool = False,
+                     out: Tensor | None = None) -> Tensor:
+    """q / k / v bf16 (T_total, H*64) views with unit last stride (column slices of one packed QKV projection), seq from
+    seq_lens -> (T_total, H*64) bf16: every sequence attends to itself only (pm_attention_varlen_bf16).  ``out``: a bf16
+    (T_total, H*64) tensor with unit last stride to write instead of a new one; rows of no sequence are not written."""
+    _seq(seq, "attention_varlen", q, k, v, out)
+    _need(q.dim() == 2 and k.shape == q.shape and v.shape == q.shape, "attention_varlen: operands must be (T_total, H*hd), one shape")
+    T, D = q.shape
+    _need(T == seq.total, f"attention_varlen: {T} rows for lengths that sum to {seq.total}")
+    _need(n_heads >= 1 and D == n_heads * 64, f"attention_varlen: head_dim 64 only (width {D}, {n_heads} heads)")
+    for t in (q, k, v):
+        _need(t.dtype == torch.bfloat16 and t.stride(1) == 1, "attention_varlen: bf16 operands with unit last stride")
+    if out is None:
+        out = torch.empty((T, D), dtype=torch.bfloat16, device=q.device)
+    _need(out.shape == (T, D) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "attention_varlen: out must be bf16 (T_total, H*64)")
+    if T == 0:
+        return out
+    work = 4.0 * n_heads * 64 * sum(n * n for n in seq.lengths)
+    rc = _launch("attention_varlen", work, lambda: lib().pm_attention_varlen_bf16(
+        q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(), out.stride(0),
+        seq.cu.data_ptr(), seq.B, n_heads, seq.max_len, int(causal), _stream()))
+    check(rc, f"pm_attention_varlen_bf16(B={seq.B}, H={n_heads}, T={T}, max_len={seq.max_len})")
+    return out
+
+
+def embed_tokens_varlen(tokens: Tensor, emb: Tensor, pos: Tensor | None, seq: SeqLens, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """tokens int64 (B, L) right-padded -> packed (T_total, d): row cu[b] + t = emb[tokens[b, t]] + pos[t] for t < len_b.  A bf16
+    table makes ``out_dtype`` rows, an fp32 table fp32 rows, like embed_tokens.  Ids are range-checked at valid positions only."""
+    _seq(seq, "embed_tokens_varlen", tokens, emb, pos)
+    _need(tokens.dim() == 2 and tokens.dtype == torch.int64, "embed_tokens_varlen: tokens must be int64 (B, L)")
+    tokens = tokens.contiguous()
+    B, L = tokens.shape
+    V, d = emb.shape
+    _need(B == seq.B and L == seq.L, f"embed_tokens_varlen: tokens {(B, L)} against lengths for {(seq.B, seq.L)}")
+    _need(emb.dtype in (torch.bfloat16, torch.float32) and emb.is_contiguous(), "embed_tokens_varlen: emb bf16 or f32 (V, d)")
+    if EMBED_CHECK_IDS and seq.total and not torch.cuda.is_current_stream_capturing():
+        valid = torch.arange(L, device=tokens.device)[None, :] < (seq.cu[1:] - seq.cu[:-1])[:, None]
+        bad = valid & ((tokens < 0) | (tokens >= V))
+        if bool(bad.any()):
+            raise IndexError(f"embed_tokens_varlen: token id {tokens[bad][0].item()} outside the vocabulary [0, {V})")
+    if pos is not None:
+        _need(pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d and pos.shape[0] >= seq.max_len,
+              f"embed_tokens_varlen: need {seq.max_len} position rows, have {pos.shape[0]}")
+    if emb.dtype == torch.float32:
+        out_dtype = torch.float32
+    out = torch.empty((seq.total, d), dtype=out_dtype, device=emb.device)
+    rc = lib().pm_embed_tokens_varlen(tokens.data_ptr(), emb.data_ptr(), _dt(emb), pos.data_ptr() if pos is not None else None,
+                                      seq.cu.data_ptr(), out.data_ptr(), _dt(out), B, L, d, V, _stream())
+    check(rc, f"pm_embed_tokens_varlen(B={B}, L={L}, d={d}, T={seq.total})")
+    return out
+
+
+def _padded(x: Tensor, seq: SeqLens, what: str) -> tuple[int, int, int]:
+    _need(x.dim() == 3 and x.dtype in (torch.bfloat16, torch.float32) and x.stride(2) == 1, f"{what}: (B, L, d) bf16 or f32 with unit last stride")
+    B, L, d = x.shape
+    _need(B == seq.B and L == seq.L, f"{what}: {(B, L)} rows against lengths for {(seq.B, seq.L)}")
+    eb = x.element_size()
+    _need((d * eb) % 16 == 0 and (x.stride(0) * eb) % 16 == 0 and (x.stride(1) * eb) % 16 == 0 and x.stride(1) >= d,
+          f"{what}: rows and strides must be multiples of 16 bytes")
+    return B, L, d
+
+
+def rows_pack(x: Tensor, seq: SeqLens) -> Tensor:
+    """padded (B, L, d) -> packed (T_total, d): row cu[b] + t = x[b, t] for t < len_b (pm_rows_pack; padded rows are not read)."""
+    _seq(seq, "rows_pack", x)
+    B, L, d = _padded(x, seq, "rows_pack")
+    out = torch.empty((seq.total, d), dtype=x.dtype, device=x.device)
+    rc = _launch("rows_pack", (0.0, 2.0 * seq.total * d * x.element_size()), lambda: lib().pm_rows_pack(
+        x.data_ptr(), x.stride(0), x.stride(1), seq.cu.data_ptr(), out.data_ptr(), out.stride(0), B, L, d, x.element_size(), _stream()))
+    check(rc, f"pm_rows_pack(B={B}, L={L}, d={d})")
+    return out
+
+
+def rows_unpack(x: Tensor, seq: SeqLens) -> Tensor:
+    """packed (T_total, d) -> padded (B, L, d) contiguous, rows t >= len_b zero (pm_rows_unpack)."""
+    _seq(seq, "rows_unpack", x)
+    _need(x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float32) and x.stride(1) == 1 and x.shape[0] == seq.total,
+          f"rows_unpack: packed ({seq.total}, d) bf16 or f32 with unit last stride")
+    d, eb = x.shape[1], x.element_size()
+    _need((d * eb) % 16 == 0 and (x.stride(0) * eb) % 16 == 0 and x.stride(0) >= d, "rows_unpack: rows and strides must be multiples of 16 bytes")
+    out = torch.empty((seq.B, seq.L, d), dtype=x.dtype, device=x.device)
+    rc = _launch("rows_unpack", (0.0, float(seq.total + seq.B * seq.L) * d * eb), lambda: lib().pm_rows_unpack(
+        x.data_ptr(), x.stride(0), seq.cu.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), seq.B, seq.L, d, eb, _stream()))
+    check(rc, f"pm_rows_unpack(B={seq.B}, L={seq.L}, d={d})")
+    return out
+
+
+def rows_zero_tail(x: Tensor, seq: SeqLens) -> Tensor:
+    """Zeroes rows t >= len_b of a padded (B, L, d) tensor IN PLACE and returns it (pm_rows_zero_tail)."""
+    _seq(seq, "rows_zero_tail", x)
+    B, L, d = _padded(x, seq, "rows_zero_tail")
+    rc = _launch("rows_zero_tail", (0.0, float(B * L - seq.total) * d * x.element_size()), lambda: lib().pm_rows_zero_tail(
+        x.data_ptr(), x.stride(0), x.stride(1), seq.cu.data_ptr(), B, L, d, x.element_size(), _stream()))
+    check(rc, f"pm_rows_zero_tail(B={B}, L={L}, d={d})")
+    return x
+
+
+def segment_mean(x: Tensor, seq: SeqLens) -> Tensor:
+    """packed (T_total, d) bf16 or f32 -> f32 (B, d): the mean of each sequence's rows, fp32 sums in row order (pm_segment_mean)."""
+    _seq(seq, "segment_mean", x)
+    _need(x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float32) and x.stride(1) == 1 and x.shape[0] == seq.total,
+          f"segment_mean: packed ({seq.total}, d) bf16 or f32 with unit last stride")
+    d, eb = x.shape[1], x.element_size()
+    _need((d * eb) % 16 == 0 and (x.stride(0) * eb) % 16 == 0 and x.stride(0) >= d and seq.B <= 65535,
+          "segment_mean: rows and strides must be multiples of 16 bytes, at most 65535 sequences")
+    out = torch.empty((seq.B, d), dtype=torch.float32, device=x.device)
+    rc = _launch("segment_mean", (float(seq.total * d), float(seq.total * d * eb)), lambda: lib().pm_segment_mean(
+        x.data_ptr(), x.stride(0), _dt(x), seq.cu.data_ptr(), out.data_ptr(), seq.B, d, _stream()))
+    check(rc, f"pm_segment_mean(B={seq.B}, d={d}, T={seq.total})")
+    return out

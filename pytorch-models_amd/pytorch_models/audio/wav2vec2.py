@@ -14,7 +14,10 @@ never happen and each piece lands on a kernel that already exists for the transf
                                group's weight streamed; bias, GELU and the "+ x" residual in its epilogue)
     layers, norm            -> transformer.Encoder / LayerNorm
 
-No CPU path, inference only (dropout is the identity).
+    forward(x, lengths=)    -> pm_rows_zero_tail in front of pe_conv, pm_rows_pack behind it, Encoder.forward_packed
+                               (pm_attention_varlen_bf16) and pm_rows_unpack: a batch of clips of different lengths
+
+No CPU path (but for the lengths= call, whose plain-torch form is in _cpu.py), inference only (dropout is the identity).
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import json
 import torch
 from torch import Tensor, nn
 
+from .. import _cpu
 from .._hip import ops
 from ..transformer import Encoder, LayerNorm, Linear, _f32, derived, require_bf16_params
 
@@ -169,8 +173,23 @@ class Wav2Vec2(nn.Module):
         require_bf16_params(self, type(self).__name__)
         return self.proj(self.feature_encoder.time_major(x))  # (B, T, d) bf16
 
-    def forward(self, x: Tensor) -> Tensor:
-        """waveform (B, L) -> (B, T, d)."""
+    @classmethod
+    def frame_length(cls, n: int) -> int:
+        """Frames the stem makes of ``n`` samples: n -> (n - k) // s + 1 through its own (kernel, stride) chain (0 when too short)."""
+        for k, s in zip(cls.STEM_KERNELS, cls.STEM_STRIDES):
+            n = (n - k) // s + 1 if n >= k else 0
+        return n
+
+    def forward(self, x: Tensor, lengths=None) -> Tensor:
+        """waveform (B, L) -> (B, T, d).
+        ``lengths`` (B ints or an integer tensor, in samples, each in 400..L; ``x`` right-padded): a batch of clips of different
+        lengths.  Row b on its first frame_length(lengths[b]) frames is what forward(x[b:b+1, :lengths[b]]) returns, the frames
+        past them are exactly 0.  The stem is local (valid convolutions, per-frame norms), so its valid frames do not see
+        the padding; the frames past each clip are zeroed BEFORE the positional convolution - alone, that
+        convolution sees zero padding exactly where the batch now holds zeros - and the encoder runs on the packed valid frames
+        (Encoder.forward_packed).  Not for ``stem_legacy``: its first layer normalises over time."""
+        if lengths is not None:
+            return self._forward_lengths(x, lengths)
         h = self._features(x)
         pad = self.pe_conv[0].padding
         h = self.grouped_conv(self.pe_conv[1], h, (pad[0], pad[1]), "gelu", h)  # x + GELU(conv(x))
@@ -178,6 +197,41 @@ class Wav2Vec2(nn.Module):
         if self.pre_norm:
             return self.norm(self.layers(h), out_dtype)
         return self.layers(self.norm(h)).to(out_dtype)
+
+    def _forward_lengths(self, x: Tensor, lengths) -> Tensor:
+        if type(self).forward is not Wav2Vec2.forward or not isinstance(self.pe_conv[1], nn.Conv1d):
+            raise NotImplementedError(f"{type(self).__name__}: variable-length batches are implemented for Wav2Vec2 / HuBERT only")
+        if isinstance(self.feature_encoder[0][2], nn.InstanceNorm1d):
+            raise NotImplementedError(
+                "Wav2Vec2: lengths= is not available with stem_legacy=True: its first layer normalises every channel over TIME, "
+                "so the padding of a batch changes the statistics - and with them every valid frame - of the shorter clips")
+        if x.dim() == 3:
+            x = x.squeeze(1)
+        if x.dim() != 2:
+            raise ValueError(f"Wav2Vec2: with lengths the waveform must be (B, L), got {tuple(x.shape)}")
+        B, L = x.shape
+        samples = ops.seq_lens(lengths, L, "cpu", lo=400)  # ValueError outside 400..L
+        if samples.B != B:
+            raise ValueError(f"Wav2Vec2: {samples.B} lengths for a batch of {B}")
+        frames = [self.frame_length(n) for n in samples.lengths]
+        pad = self.pe_conv[0].padding
+        out_dtype = self.norm.weight.dtype
+        if _cpu.on_cpu(x, self.norm.weight):
+            h = _cpu.w2v_features(self, x)
+            seq = ops.seq_lens(frames, h.shape[1], x.device, lo=1)
+            for b, n in enumerate(frames):
+                h[b, n:] = 0
+            h = _cpu.rows_pack(_cpu.w2v_positional(self, h), frames)
+        else:
+            h = self._features(x)
+            seq = ops.seq_lens(frames, h.shape[1], h.device, lo=1)
+            h = ops.rows_zero_tail(h, seq)
+            h = ops.rows_pack(self.grouped_conv(self.pe_conv[1], h, (pad[0], pad[1]), "gelu", h), seq)
+        if self.pre_norm:
+            h = self.norm(self.layers.forward_packed(h, seq), out_dtype)
+        else:
+            h = self.layers.forward_packed(self.norm(h), seq).to(out_dtype)
+        return ops.rows_unpack(h, seq) if h.is_cuda else _cpu.rows_unpack(h, frames, seq.L)
 
     @classmethod
     def from_hf(cls, model_tag: str, *, pretrained: bool = False, config: dict | str | None = None, **kwargs):

@@ -276,6 +276,31 @@ class MHA(nn.Module):
         return y.view(*lead, Lq, y.shape[-1])
 
 
+    def attend_packed(self, x: Tensor, seq: "ops.SeqLens", causal: bool = False, residual: Tensor | None = None) -> Tensor:
+        """Self-attention over a packed ragged batch: ``x`` is (T_total, d), the rows of sequence b are cu[b] .. cu[b + 1] of
+        ``seq`` (ops.seq_lens), and every sequence attends to itself only.  One QKV GEMM over all rows, pm_attention_varlen_bf16
+        reading the packed projection in place, out_proj with ``residual`` (T_total, d) in its epilogue - attend() without a
+        padded row anywhere.  bf16 parameters and head_dim 64 only."""
+        if _cpu.on_cpu(x, self.q_proj.weight):
+            return _cpu.mha_packed(self, x, seq, causal, residual)
+        _require_bf16(x, self.q_proj.weight, "MHA.attend_packed")
+        if _is32(self.q_proj.weight):
+            raise NotImplementedError("MHA.attend_packed: bf16 parameters only (the variable-length attention kernel is bf16); "
+                                      "call model.to(torch.bfloat16)")
+        if self.head_dim != 64:
+            raise NotImplementedError(f"MHA.attend_packed: head_dim 64 only (got {self.head_dim})")
+        if self.training and self.dropout > 0.0:
+            raise NotImplementedError("MHA: inference only (attention dropout is not implemented)")
+        if x.dim() != 2 or x.shape[0] != seq.total:
+            raise ValueError(f"MHA.attend_packed: x must be (T_total = {seq.total}, d), got {tuple(x.shape)}")
+        inner = self.n_heads * self.head_dim
+        w, b = self._pack("qkv")
+        qkv = ops.linear(_xb(x), w, b)
+        o = ops.attention_varlen(qkv[:, :inner], qkv[:, inner : 2 * inner], qkv[:, 2 * inner :], self.n_heads, seq, causal)
+        return ops.linear(o, _wb(self.out_proj, "w", self.out_proj.weight), _f32(self.out_proj, "b", self.out_proj.bias),
+                          resid=residual, out_dtype=x.dtype)
+
+
 def _bias4(attn_bias: Tensor, lead, Lq: int, Lk: int) -> Tensor:
     """additive float bias or boolean keep-mask, broadcastable to (*lead, H, Lq, Lk) -> f32 (b, h, Lq, Lk) with unit key
     stride and a non-zero query stride (batch / head strides may be 0)."""
@@ -445,6 +470,17 @@ class EncoderLayer(DecoderLayer):
 
     def forward(self, x: Tensor) -> Tensor:
         return DecoderLayer.forward(self, x, None)
+
+    def forward_packed(self, x: Tensor, seq: "ops.SeqLens") -> Tensor:
+        """forward() over a packed ragged batch (T_total, d): every operator but the attention is row-wise and runs on the
+        packed rows as they are; the attention is MHA.attend_packed.  Pre- and post-norm as forward()."""
+        if type(self.sa).forward is not MHA.forward or type(self.mlp).forward is not MLP.forward:
+            raise NotImplementedError("EncoderLayer.forward_packed: plain MHA / MLP blocks only")
+        if self.pre_norm:
+            x = self.sa.attend_packed(self.sa_norm(x), seq, False, residual=x)
+            return self.mlp.run(self.mlp_norm(x), residual=x)
+        x = self.sa_norm(self.sa.attend_packed(x, seq, False, residual=x))
+        return self.mlp_norm(self.mlp.run(x, residual=x))
 
     # ---- LayerNorm folded into the GEMMs on either side of it (Encoder.forward drives this)
     def chain_ok(self, x: Tensor) -> bool:
@@ -645,6 +681,15 @@ class Encoder(nn.Sequential):
         for st in streams[1:]:
             cur.wait_stream(st)
         return out[:, 0] if first_row and not tail else out
+
+    def forward_packed(self, x: Tensor, seq: "ops.SeqLens") -> Tensor:
+        """The layers in order over a packed ragged batch (T_total, d) with the extents ``seq`` (ops.seq_lens), on the caller's
+        stream.  LayerNorms run as their own kernels (no fold, no two-stream schedule: forward() is untouched)."""
+        for layer in self:
+            if not isinstance(layer, EncoderLayer):
+                raise NotImplementedError("Encoder.forward_packed: EncoderLayer children only")
+            x = layer.forward_packed(x, seq)
+        return x
 
     def split_sizes(self, batch: int, tokens: int, dtype: torch.dtype, device: torch.device):
         """[(lo, hi), ...] = the batch ranges forward() would run on separate streams for a (batch, tokens, d) input, or None."""

@@ -22,5 +22,5 @@ for l in out.splitlines():
         k, v = t.split(":", 1)
         cur[k.strip()] = v.strip()
 for r in rows:
-    print(f"{r['name'][-64:]:64s} VGPR {r.get('VGPRs')} AGPR {r.get('AGPRs')} spillV {r.get('VGPRs Spill')} spillS {r.get('SGPRs Spill')} "
+    print(f"{r['name'][-64:]:64s} VGPR {r.get('VGPRs')} AGPR {r.get('AGPRs')} SGPR {r.get('TotalSGPRs')} spillV {r.get('VGPRs Spill')} spillS {r.get('SGPRs Spill')} "
           f"scratch {r.get('ScratchSize [bytes/lane]')} occ {r.get('Occupancy [waves/SIMD]')} LDS {r.get('LDS Size [bytes/block]')}")
