@@ -788,6 +788,20 @@ int pm_attention_varlen_bf16(const void* q, int64_t q_stride_t, const void* k, i
                              int64_t v_stride_t, void* o, int64_t o_stride_t, const int32_t* cu_seqlens, int64_t B,
                              int64_t H, int64_t max_len, int causal, void* stream);
 
+/* pm_attention_varlen_bf16 plus an additive bias that depends on key - query alone (T5's relative-position bias), read from a
+ * per-head distance table instead of a (B, H, L, L) one:
+ *   bias(h, i, j) = rel_lut[h * lut_stride_h + clamp(j - i, -radius, radius) + radius]      fp32, natural-log units
+ * with i, j positions inside the sequence.  rel_lut: device memory, 4-byte aligned, H rows of >= 2 * radius + 1 floats
+ * (lut_stride_h >= 2 * radius + 1, in elements); 0 <= radius <= PM_RELBIAS_MAX_RADIUS (the head's table is staged in LDS
+ * beside the K/V tiles).  Entries may be -inf (a masked distance); a row whose visible keys all carry -inf returns zeros, as
+ * pm_attention_bias_bf16 does.  Both causal values.  Per sequence the arithmetic - and the bits - are those of
+ * pm_attention_bias_bf16 on that sequence alone with the (1, H, len, len) table gathered from rel_lut. */
+#define PM_RELBIAS_MAX_RADIUS 512
+int pm_attention_varlen_relbias_bf16(const void* q, int64_t q_stride_t, const void* k, int64_t k_stride_t, const void* v,
+                                     int64_t v_stride_t, void* o, int64_t o_stride_t, const int32_t* cu_seqlens, int64_t B,
+                                     int64_t H, int64_t max_len, int causal, const float* rel_lut, int64_t lut_stride_h,
+                                     int64_t radius, void* stream);
+
 /* pm_embed_tokens into packed rows: out[cu[b] + t, :] = emb[tokens[b, t], :] + pos[t, :] for t < len_b.  tokens: int64 (B, L)
  * contiguous, right-padded (ids at t >= len_b are not read); emb: (V, d) of emb_dtype (PM_BF16 | PM_F32; an f32 table needs
  * out_dtype PM_F32); pos: f32 (>= L, d) or NULL; out: (cu[B], d) contiguous.  Ids are clamped to [0, V) like pm_embed_tokens. */

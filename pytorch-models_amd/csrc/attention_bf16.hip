@@ -30,6 +30,14 @@ __device__ __forceinline__ float ah_add_xor32(float v) {
 }
 
 
+// median of (x, 0, hi) = x clamped to [0, hi] for hi >= 0, in one instruction (hipcc emits max + min: it cannot know hi >= 0);
+// hi is wave-uniform and stays in a scalar register
+__device__ __forceinline__ int ah_clamp0(int x, int hi) {
+  int r;
+  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
+  return r;
+}
+
 constexpr int KV_TILE = 64;
 constexpr int TILE_B = KV_TILE * 128;  // 8 KiB: 64 rows x 64 bf16
 
@@ -45,15 +53,24 @@ __device__ __forceinline__ bf16x8 tr_read_pair(const char* p0, const char* p1) {
 // are not read.  A workgroup whose query block starts at or past its sequence's end returns here - a function of blockIdx alone,
 // in front of every barrier -, and nT below comes from the sequence's own length, so padded key tiles never exist.  Everything
 // behind this prologue is the one tile body: the other instantiations compile to the code they had.
-template <bool CAUSAL, bool BIAS, bool VARLEN = false>
+//
+// RELB (pm_attention_varlen_relbias_bf16; VARLEN and BIAS both set): the additive bias is a function of key - query alone,
+// read from a distance table instead of a (B, H, Lq, Lk) one: bias(h, q, k) = rel_lut[h * lut_stride_h + clamp(k - q, -R, R) + R].
+// The arguments are reused: `bias` is rel_lut, `bsh` is lut_stride_h, `bsb` is R, `bsq` is not read.  The head's 2R + 1 floats
+// go into LDS once, behind the K/V staging area, in front of the first barrier; only where the eight groups bq[kb][gq] come
+// from differs from the BIAS form (a clamped index and a ds_read per score instead of a global load per four), so a sequence's
+// rows carry the bits pm_attention_bias_bf16 gives on that sequence alone with the gathered (1, H, n, n) table.
+constexpr int RELB_MAX_RADIUS = PM_RELBIAS_MAX_RADIUS;        // 2R + 1 floats <= 4100 bytes beside the 32 KiB of K/V staging
+constexpr int RELB_LDS = ((2 * RELB_MAX_RADIUS + 1) * 4 + 15) & ~15;
+template <bool CAUSAL, bool BIAS, bool VARLEN = false, bool RELB = false>
 __global__ __launch_bounds__(256) void attn_fwd_hd64(const bf16* __restrict__ Q, int64_t qsb, int64_t qst,
                                                      const bf16* __restrict__ K, int64_t ksb, int64_t kst,
                                                      const bf16* __restrict__ V, int64_t vsb, int64_t vst,
                                                      bf16* __restrict__ O, int64_t osb, int64_t ost, int H, int Lq_arg,
                                                      int Lk_arg, int nqb, const float* __restrict__ bias, int64_t bsb,
                                                      int64_t bsh, int64_t bsq, const int* __restrict__ cu) {
-  static_assert(!(VARLEN && BIAS), "the variable-length form takes no bias");
-  __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];  // [buf][K, V]
+  static_assert((VARLEN && BIAS) == RELB, "the variable-length form takes its bias from a distance table only");
+  __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B + (RELB ? RELB_LDS : 0)];  // [buf][K, V] (+ RELB: the head's table)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -121,8 +138,17 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64(const bf16* __restrict__ Q,
   const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
 
   const bool wave_live = q0 + wave * 32 < Lq;
-  const float* bias_row = BIAS ? bias + (int64_t)b * bsb + (int64_t)h * bsh + (int64_t)qi_ld * bsq : nullptr;
-  const bool bias_vec = BIAS && !(((uintptr_t)bias | (uintptr_t)(bsb * 4) | (uintptr_t)(bsh * 4) | (uintptr_t)(bsq * 4)) & 15);
+  const float* bias_row = BIAS && !RELB ? bias + (int64_t)b * bsb + (int64_t)h * bsh + (int64_t)qi_ld * bsq : nullptr;
+  const bool bias_vec = BIAS && !RELB && !(((uintptr_t)bias | (uintptr_t)(bsb * 4) | (uintptr_t)(bsh * 4) | (uintptr_t)(bsq * 4)) & 15);
+  // RELB: byte offset into the table of key k for this lane's query = 4 * (k + R - q), clamped to [0, 8R]: an add, a median and
+  // a ds_read per score
+  [[maybe_unused]] const char* lut_s = smem + 4 * TILE_B;
+  [[maybe_unused]] const int rel_hi = RELB ? 8 * (int)bsb : 0;
+  [[maybe_unused]] const int rel_q = RELB ? 4 * ((int)bsb - qi_ld) : 0;
+  if constexpr (RELB) {
+    const float* lut = bias + (int64_t)h * bsh;
+    for (int i = tid; i <= 2 * (int)bsb; i += 256) ((float*)(smem + 4 * TILE_B))[i] = lut[i];  // visible behind the barrier below
+  }
   load_tile(0);
   write_tile(smem);
   __syncthreads();
@@ -167,7 +193,10 @@ _Pragma("unroll")                                                               
 _Pragma("unroll")                                                                                                        \
         for (int gq = 0; gq < 4; ++gq) {                                                                                 \
           const int key = key_base + kb * 32 + 8 * gq;                                                                   \
-          if (bias_vec && key + 3 < Lk) {                                                                                \
+          if constexpr (RELB) {  /* neighbouring lanes own neighbouring queries: a half-wave reads consecutive words */   \
+_Pragma("unroll")                                                                                                        \
+            for (int e = 0; e < 4; ++e) bq[kb][gq][e] = *(const float*)(lut_s + ah_clamp0(4 * (key + e) + rel_q, rel_hi)); \
+          } else if (bias_vec && key + 3 < Lk) {                                                                         \
             bq[kb][gq] = *(const f32x4*)(bias_row + key);                                                                \
           } else {                                                                                                       \
 _Pragma("unroll")                                                                                                        \
@@ -820,6 +849,37 @@ extern "C" int pm_attention_varlen_bf16(const void* q, int64_t q_stride_t, const
   if (causal) PM_ATTV(true);
   else PM_ATTV(false);
 #undef PM_ATTV
+  PM_CHECK_LAUNCH();
+  return PM_OK;
+}
+
+/* The same with T5's relative-position bias from a per-head distance table (attn_fwd_hd64<., true, true, true>). */
+extern "C" int pm_attention_varlen_relbias_bf16(const void* q, int64_t q_stride_t, const void* k, int64_t k_stride_t,
+                                                const void* v, int64_t v_stride_t, void* o, int64_t o_stride_t,
+                                                const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t max_len, int causal,
+                                                const float* rel_lut, int64_t lut_stride_h, int64_t radius, void* stream) {
+  if (!q || !k || !v || !o || !cu_seqlens || !rel_lut || B < 0 || H <= 0 || max_len <= 0) return PM_EINVAL;
+  if (radius < 0 || radius > RELB_MAX_RADIUS || lut_stride_h < 2 * radius + 1) return PM_EINVAL;
+  if ((q_stride_t | k_stride_t | v_stride_t) % 8) return PM_EALIGN;
+  if (o_stride_t % 4) return PM_EALIGN;
+  if (q_stride_t < H * 64 || k_stride_t < H * 64 || v_stride_t < H * 64 || o_stride_t < H * 64) return PM_EINVAL;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return PM_EALIGN;
+  if ((uintptr_t)o & 7) return PM_EALIGN;
+  if (((uintptr_t)cu_seqlens | (uintptr_t)rel_lut) & 3) return PM_EALIGN;
+  if (max_len > (1 << 24)) return PM_EINVAL;
+  if (B == 0) return PM_OK;
+  const int nqb = (int)((max_len + 127) / 128);
+  const int64_t nblk = B * H * nqb;
+  if (nblk > 0x7fffffff) return PM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+#define PM_ATTR(C_)                                                                                                      \
+  hipLaunchKernelGGL((attn_fwd_hd64<C_, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, (const bf16*)q,       \
+                     (int64_t)0, q_stride_t, (const bf16*)k, (int64_t)0, k_stride_t, (const bf16*)v, (int64_t)0, v_stride_t, \
+                     (bf16*)o, (int64_t)0, o_stride_t, (int)H, (int)max_len, (int)max_len, nqb, rel_lut, radius,         \
+                     lut_stride_h, (int64_t)0, (const int*)cu_seqlens)
+  if (causal) PM_ATTR(true);
+  else PM_ATTR(false);
+#undef PM_ATTR
   PM_CHECK_LAUNCH();
   return PM_OK;
 }

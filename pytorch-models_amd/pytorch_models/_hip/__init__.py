@@ -127,6 +127,7 @@ SIGNATURES = {
     "pm_align_dtw_f32": ([_p, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
     "pm_align_ws_bytes": ([_l, _l, _l], c_int64),
     "pm_attention_varlen_bf16": ([_p, _l, _p, _l, _p, _l, _p, _l, _p, _l, _l, _l, _i, _p], c_int),
+    "pm_attention_varlen_relbias_bf16": ([_p, _l, _p, _l, _p, _l, _p, _l, _p, _l, _l, _l, _i, _p, _l, _l, _p], c_int),
     "pm_embed_tokens_varlen": ([_p, _p, _i, _p, _p, _p, _i, _l, _l, _l, _l, _p], c_int),
     "pm_rows_pack": ([_p, _l, _l, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
     "pm_rows_unpack": ([_p, _l, _p, _p, _l, _l, _l, _l, _l, _l, _p], c_int),

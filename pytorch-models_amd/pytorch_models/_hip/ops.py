@@ -1750,12 +1750,27 @@ def _seq(seq: SeqLens, what: str, *ts: Tensor) -> None:
     _cuda(seq.cu, *ts)
 
 
+RELBIAS_MAX_RADIUS = 512  # PM_RELBIAS_MAX_RADIUS of include/pm_mi355x.h: the head's table is staged in LDS
+
+
 def attention_varlen(q: Tensor, k: Tensor, v: Tensor, n_heads: int, seq: SeqLens, causal: bool = False,
-                     out: Tensor | None = None) -> Tensor:
+                     out: Tensor | None = None, *, rel_lut: Tensor | None = None, radius: int | None = None) -> Tensor:
     """q / k / v bf16 (T_total, H*64) views with unit last stride (column slices of one packed QKV projection), seq from
     seq_lens -> (T_total, H*64) bf16: every sequence attends to itself only (pm_attention_varlen_bf16).  ``out``: a bf16
-    (T_total, H*64) tensor with unit last stride to write instead of a new one; rows of no sequence are not written."""
-    _seq(seq, "attention_varlen", q, k, v, out)
+    (T_total, H*64) tensor with unit last stride to write instead of a new one; rows of no sequence are not written.
+    ``rel_lut`` f32 (H, >= 2 * radius + 1) with unit last stride adds bias(h, i, j) = rel_lut[h, clamp(j - i, -radius, radius)
+    + radius] to the scores (natural-log units, -inf allowed; i, j positions inside the sequence):
+    pm_attention_varlen_relbias_bf16, T5's relative-position bias without a (B, H, L, L) table."""
+    _need((rel_lut is None) == (radius is None), "attention_varlen: rel_lut and radius come together")
+    if rel_lut is not None:  # checked in front of everything that could launch
+        _need(isinstance(rel_lut, Tensor) and rel_lut.dtype == torch.float32 and rel_lut.device == q.device,
+              "attention_varlen: rel_lut must be an f32 tensor on the operands' device")
+        _need(isinstance(radius, int) and not isinstance(radius, bool) and 0 <= radius <= RELBIAS_MAX_RADIUS,
+              f"attention_varlen: radius must be an int in [0, {RELBIAS_MAX_RADIUS}], got {radius!r}")
+        _need(rel_lut.dim() == 2 and rel_lut.shape[0] == n_heads and rel_lut.shape[1] >= 2 * radius + 1,
+              f"attention_varlen: rel_lut must be ({n_heads}, >= {2 * radius + 1}), got {tuple(rel_lut.shape)}")
+        _need(rel_lut.stride(1) == 1 and rel_lut.stride(0) >= 2 * radius + 1, "attention_varlen: rel_lut needs unit last stride and rows that do not overlap")
+    _seq(seq, "attention_varlen", q, k, v, out, rel_lut)
     _need(q.dim() == 2 and k.shape == q.shape and v.shape == q.shape, "attention_varlen: operands must be (T_total, H*hd), one shape")
     T, D = q.shape
     _need(T == seq.total, f"attention_varlen: {T} rows for lengths that sum to {seq.total}")
@@ -1768,6 +1783,12 @@ def attention_varlen(q: Tensor, k: Tensor, v: Tensor, n_heads: int, seq: SeqLens
     if T == 0:
         return out
     work = 4.0 * n_heads * 64 * sum(n * n for n in seq.lengths)
+    if rel_lut is not None:
+        rc = _launch("attention_varlen_relbias", work, lambda: lib().pm_attention_varlen_relbias_bf16(
+            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(), out.stride(0),
+            seq.cu.data_ptr(), seq.B, n_heads, seq.max_len, int(causal), rel_lut.data_ptr(), rel_lut.stride(0), radius, _stream()))
+        check(rc, f"pm_attention_varlen_relbias_bf16(B={seq.B}, H={n_heads}, T={T}, max_len={seq.max_len}, radius={radius})")
+        return out
     rc = _launch("attention_varlen", work, lambda: lib().pm_attention_varlen_bf16(
         q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(), out.stride(0),
         seq.cu.data_ptr(), seq.B, n_heads, seq.max_len, int(causal), _stream()))

@@ -10,7 +10,11 @@ reference's way loads unchanged).
     token embedding, classifier       -> pm_embed_tokens (no positional term), pm_linear_bf16 (fp32 logits)
 
 The bucket table of RelativePositionBias is index arithmetic on the host (as in the reference, t5.py:49-70), cached per
-length; the (heads, L, L) bias is gathered from the parameter on the device.  Inference only; no CPU path."""
+length; the (heads, L, L) bias is gathered from the parameter on the device.  Inference only; no CPU path.
+
+Right-padded source batches (encode(x, lengths), forward / score(..., src_lengths=), generate(..., packed=True)) run the encoder
+on the valid rows only (forward_packed): the bias then comes from RelativePositionBias.lut, an (heads, 2 * max_distance + 1) table
+by distance that pm_attention_varlen_relbias_bf16 reads inside the kernel, and no (heads, L, L) tensor exists on that path."""
 from __future__ import annotations
 
 import math
@@ -92,6 +96,21 @@ class RelativePositionBias(nn.Module):
             cache[key] = self.buckets(length, bidirection).to(self.bias.device)
         return self.bias[:, cache[key]]  # (heads, L, L)
 
+    def lut(self, bidirection: bool) -> Tensor:
+        """The same bias by distance: fp32 (heads, 2 R + 1), R = max_distance, lut[:, d + R] = the bias of key - query = d
+        clamped to [-R, R] - the bucket depends on the distance alone and no longer changes once |d| >= max_distance, so this
+        table holds all of forward(L, bidirection) for every L.  One-sided: d > 0 holds the bucket-0 value, as the dense table
+        does above its diagonal.  Gathered from the parameter with buckets() itself; a derived value per direction, rebuilt
+        when the parameter changes (in place, storage, dtype or device).  Works on CPU tensors."""
+        R = self.max_distance
+
+        def build():
+            b = self.buckets(R + 1, bidirection)  # b[q, k]
+            row = torch.cat([b[R, :R], b[0]])  # d = -R .. -1 seen from query R, d = 0 .. R seen from query 0
+            return self.bias.detach().float()[:, row.to(self.bias.device)].contiguous()
+
+        return derived(self, f"lut{int(bool(bidirection))}", (self.bias,), build)
+
 
 class T5Block(nn.Module):
     def __init__(self, dim: int, n_heads: int, mlp_dim: int, dropout: float = 0.0, cross_attn: bool = False) -> None:
@@ -103,14 +122,26 @@ class T5Block(nn.Module):
         self.mlp_norm = LayerNorm(dim)
         self.mlp = nn.Sequential(GEGLU(dim, mlp_dim), nn.Dropout(dropout), Linear(mlp_dim, dim, False), nn.Dropout(dropout))
 
-    def forward(self, x: Tensor, memory: Tensor | None = None, attn_bias: Tensor | None = None, causal: bool = False) -> Tensor:
+    def forward(self, x: Tensor, memory: Tensor | None = None, attn_bias: Tensor | None = None, causal: bool = False,
+                memory_bias: Tensor | None = None) -> Tensor:
+        """``memory_bias``: additive f32 bias of the cross-attention, broadcastable to (B, H, L, S) (a key mask of padded sources)."""
         x = self.sa.attend(self.sa_norm(x), attn_bias=attn_bias, causal=causal, residual=x)
         if self.ca is not None:
-            x = self.ca.attend(self.ca_norm(x), memory, residual=x)
+            x = self.ca.attend(self.ca_norm(x), memory, attn_bias=memory_bias, residual=x)
         g = self.mlp[0](self.mlp_norm(x))
         wo = self.mlp[2]
         y = ops.linear(g.reshape(-1, g.shape[-1]), _wb(wo, "w", wo.weight), None, resid=x.reshape(-1, x.shape[-1]), out_dtype=x.dtype)
         return y.view(*x.shape)
+
+    def forward_packed(self, x: Tensor, seq: "ops.SeqLens", rel_lut: Tensor, radius: int) -> Tensor:
+        """The encoder block on packed rows (T_total, d) of a ragged batch (ops.seq_lens): every stage but the attention is
+        row-wise, the attention is MHA.attend_packed with the relative-position bias read by distance from ``rel_lut``."""
+        if self.ca is not None:
+            raise NotImplementedError("T5Block.forward_packed: encoder blocks only (no cross-attention on packed rows)")
+        x = self.sa.attend_packed(self.sa_norm(x), seq, residual=x, rel_lut=rel_lut, radius=radius)
+        g = self.mlp[0](self.mlp_norm(x))
+        wo = self.mlp[2]
+        return ops.linear(g, _wb(wo, "w", wo.weight), None, resid=x, out_dtype=x.dtype)
 
 
 class T5Encoder(nn.Module):
@@ -129,6 +160,19 @@ class T5Encoder(nn.Module):
             x = layer(x, attn_bias=bias)
         return self.norm(x)
 
+    def forward_packed(self, x: Tensor, seq: "ops.SeqLens") -> Tensor:
+        """forward on the packed rows (T_total, d) of a ragged batch: no padded row, no (H, L, L) bias table - every layer reads
+        the (H, 2 * max_distance + 1) distance table inside pm_attention_varlen_relbias_bf16."""
+        require_bf16_params(self, "T5Encoder.forward_packed")
+        rp = self.attn_bias
+        if rp.max_distance > ops.RELBIAS_MAX_RADIUS:
+            raise NotImplementedError(f"T5Encoder.forward_packed: max_distance {rp.max_distance} exceeds the {ops.RELBIAS_MAX_RADIUS} the "
+                                      "packed attention kernel stages per head (PM_RELBIAS_MAX_RADIUS); run without lengths")
+        lut = rp.lut(True)
+        for layer in self.layers:
+            x = layer.forward_packed(x, seq, lut, rp.max_distance)
+        return self.norm(x)
+
 
 class T5Decoder(nn.Module):
     def __init__(self, dim: int, n_heads: int, n_layers: int, mlp_dim: int, dropout: float = 0.0) -> None:
@@ -139,11 +183,16 @@ class T5Decoder(nn.Module):
         self.norm = LayerNorm(dim)
         self.out_drop = nn.Dropout(dropout)
 
-    def forward(self, x: Tensor, memory: Tensor) -> Tensor:
+    def forward(self, x: Tensor, memory: Tensor, memory_bias: Tensor | None = None) -> Tensor:
+        """``memory_bias``: f32 (B, 1, 1, S) additive key mask of the cross-attention (-inf at padded source positions).  The
+        bias kernel takes one row per query (it refuses a query stride below S), so the mask is expanded here to a contiguous
+        (B, 1, L, S) copy - B * L * S * 4 bytes per call, shared by the layers."""
         require_bf16_params(self, "T5Decoder")
         bias = self.attn_bias(x.shape[-2], bidirection=False)  # + the causal mask, applied inside the attention kernel
+        if memory_bias is not None:  # the bias kernel wants one row per query: expanded once here, not once per layer
+            memory_bias = memory_bias.float().expand(memory.shape[0], 1, x.shape[-2], memory.shape[-2]).contiguous()
         for layer in self.layers:
-            x = layer(x, memory, attn_bias=bias, causal=True)
+            x = layer(x, memory, attn_bias=bias, causal=True, memory_bias=memory_bias)
         return self.norm(x)
 
 
@@ -163,24 +212,58 @@ class T5Model(nn.Module):
         E = _wb(self.token_embs, "E", self.token_embs.weight)
         return ops.embed_tokens(x.reshape(-1, x.shape[-1]), E, None).view(*x.shape, E.shape[1])
 
-    def encode(self, x: Tensor) -> Tensor:
-        return self.encoder(self._embed(x))
+    def encode(self, x: Tensor, lengths=None) -> Tensor:
+        """Source ids (..., S) -> memory (..., S, d).  ``lengths`` (B,), a list or an integer tensor with 0 <= len_b <= S, marks a
+        right-padded (B, S) batch: the encoder then runs on the sum(len_b) valid rows only (ops.embed_tokens_varlen,
+        T5Encoder.forward_packed, ops.rows_unpack) - row b on [:len_b] is what encode returns for x[b:b+1, :len_b], rows past
+        len_b are exactly zero and the ids there are never read."""
+        if lengths is None:
+            return self.encoder(self._embed(x))
+        require_bf16_params(self, "T5Model.encode")
+        if not isinstance(x, Tensor) or x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError("T5Model.encode: with lengths, x must be int64 (B, S), right-padded")
+        return self._encode_packed(x, ops.seq_lens(lengths, x.shape[1], x.device))
 
-    def decode(self, x: Tensor, memory: Tensor) -> Tensor:
-        h, W = self.hidden_rows(x, memory)
+    def _encode_packed(self, x: Tensor, seq: "ops.SeqLens") -> Tensor:
+        E = _wb(self.token_embs, "E", self.token_embs.weight)
+        if seq.B != x.shape[0]:
+            raise ValueError(f"T5Model.encode: {seq.B} lengths for {x.shape[0]} rows")
+        if seq.total == 0:
+            ops.check_devices(E, x)
+            return torch.zeros(*x.shape, E.shape[1], dtype=torch.bfloat16, device=E.device)
+        h = ops.embed_tokens_varlen(x, E, None, seq)
+        return ops.rows_unpack(self.encoder.forward_packed(h, seq), seq)
+
+    def _encode_src(self, x: Tensor, src_lengths, who: str):
+        """(memory, cross-attention key mask) of a right-padded source batch: the packed encoder and an f32 (B, 1, 1, S) table
+        with -inf at s >= src_lengths[b].  A row without a source token has no key to attend to and is refused."""
+        require_bf16_params(self, who)
+        if not isinstance(x, Tensor) or x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError(f"{who}: with src_lengths, x must be int64 (B, S), right-padded")
+        seq = ops.seq_lens(src_lengths, x.shape[1], x.device, lo=1)  # ValueError on a length of 0; the one upload of cu_seqlens
+        memory = self._encode_packed(x, seq)
+        S = x.shape[1]
+        dead = torch.arange(S, device=x.device)[None, :] >= (seq.cu[1:] - seq.cu[:-1])[:, None]
+        mask = torch.zeros(dead.shape, dtype=torch.float32, device=x.device).masked_fill_(dead, float("-inf"))
+        return memory, mask[:, None, None, :]
+
+    def decode(self, x: Tensor, memory: Tensor, memory_bias: Tensor | None = None) -> Tensor:
+        h, W = self.hidden_rows(x, memory, memory_bias)
         return ops.linear(h.reshape(-1, h.shape[-1]), W, None, out_dtype=torch.float32).view(*x.shape, W.shape[0])
 
-    def hidden_rows(self, x: Tensor, memory: Tensor):
+    def hidden_rows(self, x: Tensor, memory: Tensor, memory_bias: Tensor | None = None):
         """(hidden rows (..., L, d) bf16, classifier weights (V, d) bf16): what decode's last GEMM and score's kernel both read."""
-        h = self.decoder(self._embed(x), memory)
+        h = self.decoder(self._embed(x), memory) if memory_bias is None else self.decoder(self._embed(x), memory, memory_bias)
         return h, _wb(self.classifier, "w", self.classifier.weight)
 
     @torch.no_grad()
-    def score(self, x: Tensor, targets: Tensor, lengths=None, *, return_argmax: bool = False):
+    def score(self, x: Tensor, targets: Tensor, lengths=None, *, src_lengths=None, return_argmax: bool = False):
         """Teacher-forced scoring in O(B L) memory: source ids x (B, S) and decoder input ids targets (B, L) int64 - exactly what
         forward takes - -> (B, L - 1) fp32 with out[b, t] = log p(targets[b, t + 1] | targets[b, : t + 1], x[b]).  ``lengths``
         (B,), 1 <= len_b <= L, marks right-padded decoder ids: positions with t + 1 >= len_b are ignored and return 0, so
-        out.sum(-1) is the sequence log-likelihood.  ``return_argmax``: also the (B, L - 1) int64 greedy predictions.  bf16
+        out.sum(-1) is the sequence log-likelihood.  ``src_lengths`` (B,), 1 <= len_b <= S, marks right-padded source ids: the
+        packed encoder runs and the cross-attention masks the keys past len_b, so row b is score on x[b:b+1, :len_b].
+        ``return_argmax``: also the (B, L - 1) int64 greedy predictions.  bf16
         parameters on a HIP device; projection, log-softmax and gather are one kernel (ops.lm_score), the (B, L, vocab) logits
         are never stored."""
         from .gpt2 import score_gate, score_rows, score_targets
@@ -188,12 +271,18 @@ class T5Model(nn.Module):
         require_bf16_params(self, "T5Model.score")  # forward's own refusals (CPU model, fp32 parameters), in forward's order
         score_gate("T5Model.score", self.classifier.weight, x, targets)
         score_targets(targets, lengths, "T5Model.score")  # shape and lengths errors before any launch
-        h, W = self.hidden_rows(targets, self.encode(x))
+        if src_lengths is None:
+            h, W = self.hidden_rows(targets, self.encode(x))
+        else:
+            h, W = self.hidden_rows(targets, *self._encode_src(x, src_lengths, "T5Model.score"))
         return score_rows(h, W, targets, lengths, return_argmax, "T5Model.score")
 
-    def forward(self, x: Tensor, targets: Tensor) -> Tensor:
-        """token ids (..., S), (..., L) int64 -> logits (..., L, vocab) fp32 (t5.py:144-151)."""
-        return self.decode(targets, self.encode(x))
+    def forward(self, x: Tensor, targets: Tensor, src_lengths=None) -> Tensor:
+        """token ids (..., S), (..., L) int64 -> logits (..., L, vocab) fp32 (t5.py:144-151).  ``src_lengths`` (B,),
+        1 <= len_b <= S: x is a right-padded (B, S) batch (see score)."""
+        if src_lengths is None:
+            return self.decode(targets, self.encode(x))
+        return self.decode(targets, *self._encode_src(x, src_lengths, "T5Model.forward"))
 
     @torch.no_grad()
     def generate_ids(self, input_ids: Tensor, max_tokens: int = 100, pad_id: int = 0, eos_id: int = 1) -> Tensor:
@@ -210,18 +299,19 @@ class T5Model(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids: Tensor, *, lengths=None, max_new_tokens: int = 100, pad_id: int = 0, eos_id: int = 1,
-                 decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False):
+                 decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False, packed: bool = False):
         """Batched greedy generation with a KV cache (text/t5_generate.py over csrc/decode_t5.hip): the loop of generate_ids per
         row of a right-padded batch.  input_ids int64 (B, S); lengths (B,) tensor or list, None = every row is full;
         decoder_prompt int64 (B, P), teacher-forced, default one column of pad_id.  Returns ids (B, P + max_new_tokens) int64 and
         out_lengths (B,) int64 - a row that has produced eos_id emits pad_id from then on and its length counts up to and
         including the eos (eos_id < 0 never stops) - and with return_logits the fp32 last-position logits of every step,
         (B, P + max_new_tokens - 1, vocab).  graph=True captures one step into a HIP graph and replays it; graph=False issues
-        the same launches eagerly.  bf16 parameters, at most 64 sequences, d_model <= 1024 (small / base / large)."""
+        the same launches eagerly.  packed=True with lengths runs the encoder on the valid source rows only (encode(x, lengths):
+        no (B, H, S, S) bias table); the default keeps the dense-table encoder.  bf16 parameters, at most 64 sequences, d_model <= 1024 (small / base / large)."""
         from .t5_generate import generate
 
         return generate(self, input_ids, lengths=lengths, max_new_tokens=max_new_tokens, pad_id=pad_id, eos_id=eos_id,
-                        decoder_prompt=decoder_prompt, graph=graph, return_logits=return_logits)
+                        decoder_prompt=decoder_prompt, graph=graph, return_logits=return_logits, packed=packed)
 
     @staticmethod
     def from_t5x(model_tag: str, *, pretrained: bool = False, **kwargs) -> "T5Model":

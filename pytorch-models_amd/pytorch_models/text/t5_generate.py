@@ -37,6 +37,21 @@ def _interleaved_wv(geglu) -> Tensor:
                    lambda: torch.stack([w.detach(), v.detach()], 1).reshape(2 * w.shape[0], w.shape[1]).to(torch.bfloat16).contiguous())
 
 
+def encode_dense(model, input_ids: Tensor, lengths: Tensor):
+    """The padded-rectangle encoder of a lengths batch: (memory (B, S, d) bf16, bytes of its bias table).  The additive bias of
+    every encoder layer is per row - the relative bias plus -inf on the key columns >= lengths[b] - built once per call, fp32
+    (B, H, S, S); rows of padded queries hold finite garbage that nothing reads (the cross attention stops at lengths[b])."""
+    enc = model.encoder
+    x = model._embed(input_ids)
+    S = input_ids.shape[1]
+    rel = enc.attn_bias(S, bidirection=True).float()  # (H, S, S)
+    dead = torch.arange(S, device=x.device)[None, :] >= lengths[:, None]  # (B, S)
+    bias = rel[None] + torch.zeros(dead.shape, dtype=torch.float32, device=x.device).masked_fill_(dead, float("-inf"))[:, None, None, :]
+    for layer in enc.layers:
+        x = layer(x, attn_bias=bias)
+    return enc.norm(x), bias.numel() * 4
+
+
 class T5DecodeState(plan.CapturedStep):
     """State + launch list of the decode step for one (model, batch, source length, prompt length, new tokens) geometry."""
 
@@ -152,30 +167,26 @@ class T5DecodeState(plan.CapturedStep):
         self.encoder_bias_bytes = 0
 
     # ---- per call: encoder (with source padding), cross K/V, prompt
-    def encode(self, input_ids: Tensor, lengths: Tensor | None) -> Tensor:
-        """memory (B, S, d) bf16.  Padded sources: the additive bias of every encoder layer is per row - the relative bias plus
-        -inf on the key columns >= lengths[b] - built once per call, fp32 (B, H, S, S); rows of padded queries hold finite
-        garbage that nothing reads (the cross attention stops at lengths[b])."""
-        m, enc = self.model, self.model.encoder
-        x = m._embed(input_ids)
+    def encode(self, input_ids: Tensor, lengths: Tensor | None, packed: bool = False) -> Tensor:
+        """memory (B, S, d) bf16.  Padded sources: encode_dense, the padded rectangle under an fp32 (B, H, S, S) bias table.
+        ``packed`` (with lengths): the packed encoder of T5Model.encode(x, lengths) instead - no padded row is computed, the
+        bias comes from the (H, 2 * max_distance + 1) distance table inside the attention kernel, and rows past lengths[b] of
+        the memory are zero."""
+        m = self.model
+        self.encoder_bias_bytes = 0
         if lengths is None:
-            self.encoder_bias_bytes = 0
-            return enc(x)
-        S = input_ids.shape[1]
-        rel = enc.attn_bias(S, bidirection=True).float()  # (H, S, S)
-        dead = torch.arange(S, device=x.device)[None, :] >= lengths[:, None]  # (B, S)
-        bias = rel[None] + torch.zeros(dead.shape, dtype=torch.float32, device=x.device).masked_fill_(dead, float("-inf"))[:, None, None, :]
-        self.encoder_bias_bytes = bias.numel() * 4
-        for layer in enc.layers:
-            x = layer(x, attn_bias=bias)
-        return enc.norm(x)
+            return m.encoder(m._embed(input_ids))
+        if packed:
+            return m.encode(input_ids, lengths)
+        memory, self.encoder_bias_bytes = encode_dense(m, input_ids, lengths)
+        return memory
 
-    def bind(self, input_ids: Tensor, lengths: Tensor | None, prompt: Tensor | None) -> None:
+    def bind(self, input_ids: Tensor, lengths: Tensor | None, prompt: Tensor | None, packed: bool = False) -> None:
         """New sources (and prompt), same geometry: everything is written INTO the existing buffers, so the captured graph (which
         holds raw pointers) stays valid."""
         B, S = self.B, self.S
         assert tuple(input_ids.shape) == (B, S)
-        memory = self.encode(input_ids, lengths)
+        memory = self.encode(input_ids, lengths, packed)
         mem2 = memory.reshape(B * S, self.d)
         for kv, wkv in zip(self.cross_kv, self._cross_w):
             ops.linear(mem2, wkv, None, out=kv)
@@ -215,7 +226,7 @@ def _signature(model) -> tuple:
 
 @torch.no_grad()
 def generate(model, input_ids: Tensor, *, lengths=None, max_new_tokens: int = 100, pad_id: int = 0, eos_id: int = 1,
-             decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False):
+             decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False, packed: bool = False):
     require_bf16_params(model, "T5Model.generate")
     if not isinstance(input_ids, Tensor) or input_ids.dtype != torch.int64 or input_ids.dim() != 2:
         raise ValueError("T5Model.generate: input_ids must be int64 (B, S), right-padded")
@@ -248,7 +259,7 @@ def generate(model, input_ids: Tensor, *, lengths=None, max_new_tokens: int = 10
         cached = (key, T5DecodeState(model, B, S, P, int(max_new_tokens), int(pad_id), int(eos_id), bool(return_logits)))
         model.__dict__["_pm_t5_decode"] = cached
     st = cached[1]
-    st.bind(input_ids, len_t, decoder_prompt)
+    st.bind(input_ids, len_t, decoder_prompt, bool(packed))
     st.run(graph)
     out = (st.tokens.clone(), st.out_len.clone())
     return out + (st.logits.clone(),) if return_logits else out

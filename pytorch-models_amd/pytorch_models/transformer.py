@@ -276,12 +276,16 @@ class MHA(nn.Module):
         return y.view(*lead, Lq, y.shape[-1])
 
 
-    def attend_packed(self, x: Tensor, seq: "ops.SeqLens", causal: bool = False, residual: Tensor | None = None) -> Tensor:
+    def attend_packed(self, x: Tensor, seq: "ops.SeqLens", causal: bool = False, residual: Tensor | None = None,
+                      rel_lut: Tensor | None = None, radius: int | None = None) -> Tensor:
         """Self-attention over a packed ragged batch: ``x`` is (T_total, d), the rows of sequence b are cu[b] .. cu[b + 1] of
         ``seq`` (ops.seq_lens), and every sequence attends to itself only.  One QKV GEMM over all rows, pm_attention_varlen_bf16
         reading the packed projection in place, out_proj with ``residual`` (T_total, d) in its epilogue - attend() without a
-        padded row anywhere.  bf16 parameters and head_dim 64 only."""
+        padded row anywhere.  ``rel_lut`` (H, >= 2 * radius + 1) f32 and ``radius``: a relative-position bias read by distance
+        inside the kernel (ops.attention_varlen; T5).  bf16 parameters and head_dim 64 only."""
         if _cpu.on_cpu(x, self.q_proj.weight):
+            if rel_lut is not None:
+                raise RuntimeError("MHA.attend_packed: the relative-position form runs on HIP devices only (no CPU path)")
             return _cpu.mha_packed(self, x, seq, causal, residual)
         _require_bf16(x, self.q_proj.weight, "MHA.attend_packed")
         if _is32(self.q_proj.weight):
@@ -296,7 +300,8 @@ class MHA(nn.Module):
         inner = self.n_heads * self.head_dim
         w, b = self._pack("qkv")
         qkv = ops.linear(_xb(x), w, b)
-        o = ops.attention_varlen(qkv[:, :inner], qkv[:, inner : 2 * inner], qkv[:, 2 * inner :], self.n_heads, seq, causal)
+        o = ops.attention_varlen(qkv[:, :inner], qkv[:, inner : 2 * inner], qkv[:, 2 * inner :], self.n_heads, seq, causal,
+                                 rel_lut=rel_lut, radius=radius)
         return ops.linear(o, _wb(self.out_proj, "w", self.out_proj.weight), _f32(self.out_proj, "b", self.out_proj.bias),
                           resid=residual, out_dtype=x.dtype)
 
