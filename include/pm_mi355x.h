@@ -827,6 +827,50 @@ int pm_rows_zero_tail(void* x, int64_t x_stride_b, int64_t x_stride_t, const int
 int pm_segment_mean(const void* x, int64_t x_stride_t, int x_dtype, const int32_t* cu_seqlens, float* out, int64_t B,
                     int64_t d, void* stream);
 
+/* ---- CTC heads of the wav2vec2 family (csrc/ctc.hip; DESIGN.md "CTC heads").  Frames are PACKED: clip b owns the rows
+ * cu_frames[b] .. cu_frames[b + 1] (int32 (B + 1), device memory, cu[0] = 0, non-decreasing, cu[B] <= total_frames).  No atomics:
+ * a clip's outputs are bit-identical wherever it sits in the batch and whatever B is.  Ids and lengths are clamped on the
+ * device, so a bad one cannot fault; callers validate on the host.  Strides are in elements. */
+
+/* Vocabulary projection + bias + log-softmax + arg-max in one pass over the hidden rows:
+ *   x[m, v] = sum_k h[m, k] w[v, k] + bias[v]   (bf16 operands, fp32 accumulation on the MFMA, bias f32 (V) or NULL)
+ *   logp[m, v] = x[m, v] - lse[m]               f32 (M, ldl >= V); columns V .. ldl are not written
+ *   best[m] = the LOWEST index among the maxima of x[m, :V], best_logp[m] (or NULL) = logp[m, best[m]].
+ * 2 <= V <= 256, K % 8 == 0, ldh / ldw % 8 == 0, h / w 16-byte aligned, any M >= 0.  A workgroup owns 64 rows and all V
+ * columns: no second kernel, no workspace. */
+int pm_ctc_head_bf16(const void* h, int64_t ldh, const void* w, int64_t ldw, const float* bias, float* logp, int64_t ldl,
+                     int32_t* best, float* best_logp, int64_t M, int64_t V, int64_t K, void* stream);
+
+/* Best-path decoding: per clip the arg-max sequence best[cu[b] ..] with repeats merged and `blank` removed.
+ *   ids / start: int32 (B, Tmax): the emitted ids and the first frame of each, then -1;  n: int32 (B) their count.
+ *   path_logp: f32 (B) = sum of best_logp over the clip's frames (thread i of 256 adds frames i, i + 256, .. in ascending order,
+ *   a wave folds its partials with the xor butterfly 32 .. 1, the four wave sums are added in wave order); best_logp NULL <=>
+ *   path_logp NULL.  A clip of 0 frames gives n = 0; a clip longer than Tmax is cut at Tmax. */
+int pm_ctc_greedy(const int32_t* best, const int32_t* cu_frames, const float* best_logp, int32_t* ids, int32_t* n, int32_t* start,
+                  float* path_logp, int64_t total_frames, int64_t B, int64_t Tmax, int64_t blank, void* stream);
+
+/* loglik[b] = log p(targets[b, :U_b] | clip b): the CTC alpha recursion in log space over the S_b = 2 U_b + 1 extended labels
+ * (state s takes s, s - 1, and s - 2 when its label is not the blank and differs from the label at s - 2; the result merges the
+ * last two states).  logp: f32 (total_frames, ldl >= V) - pm_ctc_head_bf16's output or any f32 matrix; -inf entries are legal
+ * and give no NaN (an all -inf merge is -inf).  targets: int32 (B, ldt >= Umax) right-padded, entries at u >= U_b are never
+ * read; target_lengths: int32 (B).  An infeasible pair gives exactly -inf; U_b = 0 gives the all-blank path; a clip of 0
+ * frames gives -inf.  Umax <= 511, 0 <= blank < V. */
+int pm_ctc_forward_f32(const float* logp, int64_t ldl, const int32_t* cu_frames, const int32_t* targets, int64_t ldt,
+                       const int32_t* target_lengths, float* loglik, int64_t total_frames, int64_t B, int64_t Umax, int64_t V,
+                       int64_t blank, void* stream);
+
+/* The same recursion with max in place of the merge (one kernel template) and the backtrace on the device.  Tie rule: stay if it
+ * is not below the others, else s - 1 if it is not below s - 2, else s - 2; at the end the final blank state unless the last
+ * label state is strictly above it.  Every score is one fp32 max followed by one fp32 add: the path is bit-determined by logp.
+ *   start / stop: int32 (B, Umax): first frame and one past the last frame of each target token, -1 at u >= U_b;
+ *   score: f32 (B).  An infeasible pair gives -1 everywhere and -inf.
+ *   ws: pm_ctc_ws_bytes(B, Tmax, Umax) bytes, 16-byte aligned, no initial state (two bits per frame and state). Tmax >= every
+ *   clip's frame count (longer clips are cut). */
+int64_t pm_ctc_ws_bytes(int64_t B, int64_t Tmax, int64_t Umax);
+int pm_ctc_viterbi_f32(const float* logp, int64_t ldl, const int32_t* cu_frames, const int32_t* targets, int64_t ldt,
+                       const int32_t* target_lengths, int32_t* start, int32_t* stop, float* score, void* ws, int64_t total_frames,
+                       int64_t B, int64_t Tmax, int64_t Umax, int64_t V, int64_t blank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,3 +165,113 @@ def w2v_positional(m, h: Tensor) -> Tensor:
     pad = m.pe_conv[0].padding
     y = F.conv1d(F.pad(h.transpose(1, 2), (pad[0], pad[1])), conv.weight, conv.bias, conv.stride, groups=conv.groups)
     return h + F.gelu(y).transpose(1, 2)
+
+
+# ---- CTC heads (audio/ctc.py): the four ops of csrc/ctc.hip on packed frames, plain torch / numpy
+def ctc_head(h: Tensor, w: Tensor, b: Tensor | None):
+    """(M, K) rows -> (logp f32 (M, V), best int32 (M), best_logp f32 (M)): log_softmax of the fp32 logits, the lowest arg-max."""
+    x = F.linear(h.float(), w.float(), None if b is None else b.float())  # fp32 logits also for a bf16 module, as the kernel keeps them
+    logp = torch.log_softmax(x, -1)
+    V = x.shape[-1]
+    idx = torch.arange(V).expand_as(x)
+    best = torch.where(x == x.max(-1, keepdim=True).values, idx, torch.full_like(idx, V)).min(-1).values
+    return logp, best.to(torch.int32), logp.gather(1, best[:, None])[:, 0]
+
+
+def ctc_greedy(best: Tensor, frames, L: int, best_logp: Tensor | None, blank: int):
+    """packed arg-max ids -> (ids (B, L), n (B), start (B, L), path_logp (B) | None): repeats merged, blanks removed, then -1."""
+    B = len(frames)
+    ids = torch.full((B, L), -1, dtype=torch.int32)
+    start = torch.full((B, L), -1, dtype=torch.int32)
+    n = torch.zeros(B, dtype=torch.int32)
+    path = torch.zeros(B, dtype=torch.float32) if best_logp is not None else None
+    r0 = 0
+    for b, T in enumerate(frames):
+        a = best[r0 : r0 + T]
+        keep = a != blank
+        keep[1:] &= a[1:] != a[:-1]
+        f = torch.nonzero(keep)[:, 0]
+        n[b] = f.numel()
+        ids[b, : f.numel()] = a[f]
+        start[b, : f.numel()] = f.to(torch.int32)
+        if path is not None:
+            path[b] = best_logp[r0 : r0 + T].sum()
+        r0 += T
+    return ids, n, start, path
+
+
+def _ctc_ext(target, blank: int):
+    ext = [blank]
+    for t in target:
+        ext += [int(t), blank]
+    return ext
+
+
+def ctc_forward(logp: Tensor, frames, targets: Tensor, target_lengths, blank: int) -> Tensor:
+    """log p(target_b | clip_b) by the alpha recursion in log space (float64 inside, f32 out); -inf for an infeasible pair."""
+    import numpy as np
+
+    lp = logp.double().numpy()
+    out = np.full(len(frames), -np.inf)
+    r0 = 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for b, T in enumerate(frames):
+            ext = np.array(_ctc_ext(targets[b, : int(target_lengths[b])].tolist(), blank))
+            S = len(ext)
+            skip = np.zeros(S, dtype=bool)
+            skip[2:] = (ext[2:] != blank) & (ext[2:] != ext[:-2])
+            a = np.full(S, -np.inf)
+            a[:2] = lp[r0, ext[:2]]
+            for t in range(1, T):
+                p1 = np.concatenate(([-np.inf], a[:-1]))
+                p2 = np.where(skip, np.concatenate(([-np.inf, -np.inf], a[:-2]))[:S], -np.inf)
+                m = np.maximum(a, np.maximum(p1, p2))
+                mm = np.where(np.isfinite(m), m, 0.0)
+                a = np.where(np.isfinite(m), mm + np.log(np.exp(a - mm) + np.exp(p1 - mm) + np.exp(p2 - mm)), -np.inf) + lp[r0 + t, ext]
+            out[b] = np.logaddexp(a[-1], a[-2]) if S > 1 else a[-1]
+            r0 += T
+    return torch.from_numpy(out).float()
+
+
+def ctc_viterbi(logp: Tensor, frames, targets: Tensor, target_lengths, blank: int):
+    """The best CTC path in fp32 (one max, one add per state and frame).  Ties: stay if not below the others, else s - 1 if not
+    below s - 2, else s - 2; at the end the final blank unless the last label state is strictly above it.
+    -> (start (B, Umax), stop (B, Umax), score (B)); -1 / -inf for an infeasible pair."""
+    import numpy as np
+
+    lp = logp.float().numpy()
+    B, Umax = len(frames), targets.shape[1]
+    start = np.full((B, Umax), -1, dtype=np.int32)
+    stop = np.full((B, Umax), -1, dtype=np.int32)
+    score = np.full(B, -np.inf, dtype=np.float32)
+    ninf = np.float32(-np.inf)
+    r0 = 0
+    for b, T in enumerate(frames):
+        ext = np.array(_ctc_ext(targets[b, : int(target_lengths[b])].tolist(), blank))
+        S = len(ext)
+        skip = np.zeros(S, dtype=bool)
+        skip[2:] = (ext[2:] != blank) & (ext[2:] != ext[:-2])
+        v = np.full(S, ninf, dtype=np.float32)
+        v[:2] = lp[r0, ext[:2]]
+        bp = np.zeros((T, S), dtype=np.int8)
+        for t in range(1, T):
+            p1 = np.concatenate(([ninf], v[:-1]))
+            p2 = np.where(skip, np.concatenate(([ninf, ninf], v[:-2]))[:S], ninf)
+            stay = (v >= p1) & (v >= p2)
+            one = ~stay & (p1 >= p2)
+            bp[t] = np.where(stay, 0, np.where(one, 1, 2))
+            v = (np.where(stay, v, np.where(one, p1, p2)) + lp[r0 + t, ext]).astype(np.float32)
+        s = S - 1
+        if S > 1 and v[S - 2] > v[S - 1]:
+            s = S - 2
+        if v[s] > ninf:
+            score[b] = v[s]
+            for t in range(T - 1, -1, -1):
+                if s & 1:
+                    u = s >> 1
+                    if stop[b, u] < 0:
+                        stop[b, u] = t + 1
+                    start[b, u] = t
+                s -= int(bp[t, s]) if t else 0
+        r0 += T
+    return torch.from_numpy(start), torch.from_numpy(stop), torch.from_numpy(score)

@@ -133,6 +133,11 @@ SIGNATURES = {
     "pm_rows_unpack": ([_p, _l, _p, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
     "pm_rows_zero_tail": ([_p, _l, _l, _p, _l, _l, _l, _l, _p], c_int),
     "pm_segment_mean": ([_p, _l, _i, _p, _p, _l, _l, _p], c_int),
+    "pm_ctc_head_bf16": ([_p, _l, _p, _l, _p, _p, _l, _p, _p, _l, _l, _l, _p], c_int),
+    "pm_ctc_greedy": ([_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _p], c_int),
+    "pm_ctc_forward_f32": ([_p, _l, _p, _p, _l, _p, _p, _l, _l, _l, _l, _l, _p], c_int),
+    "pm_ctc_ws_bytes": ([_l, _l, _l], c_int64),
+    "pm_ctc_viterbi_f32": ([_p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _l, _p], c_int),
 }
 
 # Entry points of the experiment kernels (include/pm_mi355x_experiments.h; csrc/experiments/): present only in

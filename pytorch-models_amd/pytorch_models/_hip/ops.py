@@ -1881,3 +1881,146 @@ def segment_mean(x: Tensor, seq: SeqLens) -> Tensor:
         x.data_ptr(), x.stride(0), _dt(x), seq.cu.data_ptr(), out.data_ptr(), seq.B, d, _stream()))
     check(rc, f"pm_segment_mean(B={seq.B}, d={d}, T={seq.total})")
     return out
+
+
+# ---- CTC heads of the wav2vec2 family (csrc/ctc.hip; DESIGN.md, "CTC heads") ----
+CTC_MAX_VOCAB = 256    # columns one workgroup of pm_ctc_head_bf16 owns
+CTC_MAX_TARGET = 511   # labels per clip: 2 U + 1 <= 1023 states, four per thread of the recursion kernels
+
+
+def ctc_ws_bytes(B: int, Tmax: int, Umax: int) -> int:
+    return int(lib().pm_ctc_ws_bytes(B, Tmax, Umax))
+
+
+def ctc_head(h: Tensor, w: Tensor, bias: Tensor | None = None, *, want_best_logp: bool = True, out: Tensor | None = None,
+             best_out: Tensor | None = None, best_logp_out: Tensor | None = None):
+    """pm_ctc_head_bf16: h bf16 (M, K), w bf16 (V, K) (unit last strides, row strides % 8), bias f32 (V) or None ->
+    (logp f32 (M, V), best int32 (M), best_logp f32 (M) | None): logp = log_softmax(h @ w.T + bias) with fp32 accumulation, best the
+    LOWEST arg-max index of the logits, best_logp = logp[m, best[m]].  2 <= V <= 256, K % 8 == 0.  ``out``: an f32 (M, V) tensor
+    with a unit last stride (its padding columns are not written); ``best_out`` / ``best_logp_out``: contiguous (M,) buffers."""
+    _cuda(h, w, bias, out, best_out, best_logp_out)
+    _need(h.dim() == 2 and w.dim() == 2 and h.shape[1] == w.shape[1], f"ctc_head: h {tuple(h.shape)} vs w {tuple(w.shape)}")
+    _need(h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "ctc_head: h and w must be bf16")
+    _need(h.stride(1) == 1 and w.stride(1) == 1, "ctc_head: h and w must be K-contiguous")
+    M, K = h.shape
+    V = w.shape[0]
+    _need(M >= 1 and K >= 8 and K % 8 == 0, f"ctc_head: M >= 1 and K a multiple of 8, got M={M}, K={K}")
+    _need(2 <= V <= CTC_MAX_VOCAB, f"ctc_head: 2 <= V <= {CTC_MAX_VOCAB}, got {V}")
+    _need(h.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and h.stride(0) >= K and w.stride(0) >= K,
+          "ctc_head: row strides must be multiples of 8 elements")
+    _need(h.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0, "ctc_head: h and w must be 16-byte aligned")
+    if bias is not None:
+        _need(bias.dtype == torch.float32 and bias.shape == (V,) and bias.is_contiguous(), f"ctc_head: bias must be contiguous f32 ({V},)")
+    dev = h.device
+    if out is None:
+        out = torch.empty((M, V), dtype=torch.float32, device=dev)
+    _need(out.dtype == torch.float32 and out.shape == (M, V) and out.stride(1) == 1 and (out.stride(0) >= V or M == 1),
+          f"ctc_head: out must be f32 {(M, V)} with a unit last stride")
+    best = best_out if best_out is not None else torch.empty(M, dtype=torch.int32, device=dev)
+    _need(best.dtype == torch.int32 and best.shape == (M,) and best.is_contiguous(), "ctc_head: best_out must be contiguous int32 (M,)")
+    blp = best_logp_out if best_logp_out is not None else (torch.empty(M, dtype=torch.float32, device=dev) if want_best_logp else None)
+    if blp is not None:
+        _need(blp.dtype == torch.float32 and blp.shape == (M,) and blp.is_contiguous(), "ctc_head: best_logp_out must be contiguous f32 (M,)")
+    ldl = max(out.stride(0), V)
+    nbytes = float(2 * (h.numel() + w.numel()) + 4 * M * V + 8 * M)
+    rc = _launch("ctc_head", (2.0 * M * V * K, nbytes), lambda: lib().pm_ctc_head_bf16(
+        h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None, out.data_ptr(), ldl,
+        best.data_ptr(), blp.data_ptr() if blp is not None else None, M, V, K, _stream()))
+    check(rc, f"pm_ctc_head_bf16(M={M}, V={V}, K={K})")
+    return out, best, blp
+
+
+def _ctc_frames(who: str, seq: SeqLens, rows: int, *ts: Tensor) -> None:
+    _seq(seq, who, *ts)
+    _need(rows == seq.total, f"{who}: {rows} packed frames for lengths that sum to {seq.total}")
+
+
+def ctc_greedy(best: Tensor, seq: SeqLens, best_logp: Tensor | None = None, blank: int = 0):
+    """pm_ctc_greedy: best int32 (T_total) packed arg-max ids, seq from seq_lens (frames per clip, L = the padded frame count),
+    best_logp f32 (T_total) or None -> (ids int32 (B, L), n int32 (B), start int32 (B, L), path_logp f32 (B) | None): per clip the
+    arg-max sequence with repeats merged and ``blank`` removed (then -1), the count, the first frame of each emitted id (then -1)
+    and the sum of best_logp over the clip's frames.  A clip of 0 frames gives n = 0."""
+    _ctc_frames("ctc_greedy", seq, best.shape[0] if best.dim() == 1 else -1, best, best_logp)
+    _need(best.dtype == torch.int32 and best.is_contiguous(), "ctc_greedy: best must be contiguous int32 (T_total,)")
+    _need(isinstance(blank, int) and not isinstance(blank, bool) and -2 ** 31 < blank < 2 ** 31, f"ctc_greedy: blank must be an int, got {blank!r}")
+    if best_logp is not None:
+        _need(best_logp.dtype == torch.float32 and best_logp.shape == best.shape and best_logp.is_contiguous(),
+              "ctc_greedy: best_logp must be contiguous f32 (T_total,)")
+    B, L, dev = seq.B, seq.L, seq.cu.device
+    ids = torch.empty((B, L), dtype=torch.int32, device=dev)
+    start = torch.empty((B, L), dtype=torch.int32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    path = torch.empty(B, dtype=torch.float32, device=dev) if best_logp is not None else None
+    T = seq.total
+    if B == 0 or L == 0 or T == 0:  # every clip is empty: nothing to launch on
+        ids.fill_(-1)
+        start.fill_(-1)
+        n.zero_()
+        if path is not None:
+            path.zero_()
+        return ids, n, start, path
+    rc = _launch("ctc_greedy", (float(T), float(8 * T + 8 * B * L)), lambda: lib().pm_ctc_greedy(
+        best.data_ptr(), seq.cu.data_ptr(), best_logp.data_ptr() if best_logp is not None else None, ids.data_ptr(), n.data_ptr(),
+        start.data_ptr(), path.data_ptr() if path is not None else None, T, B, L, blank, _stream()))
+    check(rc, f"pm_ctc_greedy(B={B}, T={T}, L={L})")
+    return ids, n, start, path
+
+
+def _ctc_rec(who: str, logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, blank: int):
+    _need(logp.dim() == 2 and logp.dtype == torch.float32 and logp.stride(1) == 1, f"{who}: logp must be f32 (T_total, V) with a unit last stride")
+    _need(isinstance(targets, Tensor) and targets.dim() == 2 and targets.dtype == torch.int32 and (targets.shape[1] == 0 or targets.stride(1) == 1),
+          f"{who}: targets must be int32 (B, Umax) with a unit last stride")
+    _ctc_frames(who, seq, logp.shape[0], logp, targets)
+    T, V = logp.shape
+    B, Umax = targets.shape
+    _need(B == seq.B and B >= 1, f"{who}: {B} target rows for {seq.B} clips")
+    _need(V >= 1 and (logp.stride(0) >= V or T <= 1), f"{who}: rows of logp overlap")
+    _need(Umax <= CTC_MAX_TARGET, f"{who}: at most {CTC_MAX_TARGET} labels per clip, got {Umax}")
+    _need(Umax == 0 or B == 1 or targets.stride(0) >= Umax, f"{who}: rows of targets overlap")
+    _need(isinstance(blank, int) and not isinstance(blank, bool) and 0 <= blank < V, f"{who}: blank must be an int in [0, {V}), got {blank!r}")
+    _need(all(n >= 1 for n in seq.lengths), f"{who}: every clip needs at least one frame, got {seq.lengths}")
+    tl = align_counts(target_lengths, B, 0, Umax, f"{who}: target_lengths", logp.device)
+    _cuda(logp, tl)
+    return T, V, B, Umax, tl
+
+
+def ctc_forward(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, blank: int = 0, out: Tensor | None = None) -> Tensor:
+    """pm_ctc_forward_f32: logp f32 (T_total, V) packed frames (ctc_head's output or any f32 matrix, -inf allowed), seq from seq_lens
+    (every clip >= 1 frame), targets int32 (B, Umax <= 511) right-padded on the device, target_lengths host ints (checked:
+    0 <= U_b <= Umax) or a device int32 (B) -> loglik f32 (B) = log p(target_b | clip_b) by the alpha recursion in log space;
+    exactly -inf for a pair with too few frames.  Target ids are NOT validated here (the kernel clamps them)."""
+    T, V, B, Umax, tl = _ctc_rec("ctc_forward", logp, seq, targets, target_lengths, blank)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=logp.device)
+    _cuda(out)
+    _need(out.dtype == torch.float32 and out.shape == (B,) and out.is_contiguous(), f"ctc_forward: out must be contiguous f32 ({B},)")
+    rc = _launch("ctc_forward", (float(T * (2 * Umax + 1)), float(4 * T * (Umax + 1))), lambda: lib().pm_ctc_forward_f32(
+        logp.data_ptr(), max(logp.stride(0), V), seq.cu.data_ptr(), targets.data_ptr() if Umax else None, max(targets.stride(0), Umax),
+        tl.data_ptr(), out.data_ptr(), T, B, Umax, V, blank, _stream()))
+    check(rc, f"pm_ctc_forward_f32(B={B}, T={T}, Umax={Umax}, V={V})")
+    return out
+
+
+def ctc_viterbi(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, blank: int = 0, ws: Tensor | None = None):
+    """pm_ctc_viterbi_f32: operands as ctc_forward -> (start int32 (B, Umax), stop int32 (B, Umax), score f32 (B)): the first frame
+    and one past the last frame of each target token on the best path (-1 at u >= U_b) and the path's score; fp32 max and add
+    only, a fixed tie rule: the path is bit-determined by logp.  An infeasible pair gives -1 everywhere and -inf.
+    ``ws`` (uint8, ctc_ws_bytes(B, seq.max_len, Umax), 16-byte aligned): a caller-owned workspace."""
+    T, V, B, Umax, tl = _ctc_rec("ctc_viterbi", logp, seq, targets, target_lengths, blank)
+    dev = logp.device
+    start = torch.empty((B, Umax), dtype=torch.int32, device=dev)
+    stop = torch.empty((B, Umax), dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    Tmax = seq.max_len
+    nws = ctc_ws_bytes(B, Tmax, Umax)
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _cuda(ws)
+    _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws and ws.data_ptr() % 16 == 0,
+          f"ctc_viterbi: ws must hold {nws} bytes, 16-byte aligned")
+    rc = _launch("ctc_viterbi", (float(T * (2 * Umax + 1)), float(4 * T * (Umax + 1) + nws)), lambda: lib().pm_ctc_viterbi_f32(
+        logp.data_ptr(), max(logp.stride(0), V), seq.cu.data_ptr(), targets.data_ptr() if Umax else None, max(targets.stride(0), Umax),
+        tl.data_ptr(), start.data_ptr() if Umax else None, stop.data_ptr() if Umax else None, score.data_ptr(), ws.data_ptr(),
+        T, B, Tmax, Umax, V, blank, _stream()))
+    check(rc, f"pm_ctc_viterbi_f32(B={B}, T={T}, Tmax={Tmax}, Umax={Umax}, V={V})")
+    return start, stop, score

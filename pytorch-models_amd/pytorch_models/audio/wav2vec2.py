@@ -199,6 +199,12 @@ class Wav2Vec2(nn.Module):
         return self.layers(self.norm(h)).to(out_dtype)
 
     def _forward_lengths(self, x: Tensor, lengths) -> Tensor:
+        h, seq = self._packed_rows(x, lengths)
+        return ops.rows_unpack(h, seq) if h.is_cuda else _cpu.rows_unpack(h, seq.lengths, seq.L)
+
+    def _packed_rows(self, x: Tensor, lengths):
+        """forward(x, lengths=) up to its last step: (the final hidden rows of the valid frames, packed (sum frames, d); their
+        SeqLens).  The CTC head (audio/ctc.py) reads the packed rows as they are."""
         if type(self).forward is not Wav2Vec2.forward or not isinstance(self.pe_conv[1], nn.Conv1d):
             raise NotImplementedError(f"{type(self).__name__}: variable-length batches are implemented for Wav2Vec2 / HuBERT only")
         if isinstance(self.feature_encoder[0][2], nn.InstanceNorm1d):
@@ -231,7 +237,7 @@ class Wav2Vec2(nn.Module):
             h = self.norm(self.layers.forward_packed(h, seq), out_dtype)
         else:
             h = self.layers.forward_packed(self.norm(h), seq).to(out_dtype)
-        return ops.rows_unpack(h, seq) if h.is_cuda else _cpu.rows_unpack(h, frames, seq.L)
+        return h, seq
 
     @classmethod
     def from_hf(cls, model_tag: str, *, pretrained: bool = False, config: dict | str | None = None, **kwargs):

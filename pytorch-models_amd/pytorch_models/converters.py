@@ -253,6 +253,21 @@ def load_openai_gpt(model, params) -> None:
 
 
 @torch.no_grad()
+def load_hf_wav2vec2_ctc(model, state_dict: Mapping[str, Tensor]) -> list[str]:
+    """Wav2Vec2ForCTC / HubertForCTC / Data2VecAudioForCTC / SEWForCTC into audio.Wav2Vec2CTC: ``lm_head.weight`` / ``lm_head.bias``
+    into the head, every other key - under its one model prefix (``wav2vec2.``, ``hubert.``, ``data2vec_audio.``, ``sew.``) -
+    through load_hf_wav2vec2 with the encoder's own flavour.  Returns the keys it did not use."""
+    w = dict(state_dict)
+    _take(model, w, (("lm_head", "lm_head"),))
+    prefixes = {k.split(".", 1)[0] for k in w}
+    if len(prefixes) != 1:
+        raise ValueError(f"load_hf_wav2vec2_ctc: expected one model prefix in front of the encoder keys, found {sorted(prefixes)}")
+    prefix = prefixes.pop() + "."
+    return [prefix + k for k in load_hf_wav2vec2(model.encoder, {k[len(prefix):]: v for k, v in w.items()},
+                                                 flavour=model.encoder._HF_FLAVOUR)]
+
+
+@torch.no_grad()
 def load_hf_wav2vec2(model, state_dict: Mapping[str, Tensor], *, flavour: str = "wav2vec2") -> list[str]:
     """Wav2Vec2Model / HubertModel ("wav2vec2"), Data2VecAudioModel ("data2vec"), SEWModel ("sew"): conv stem, feature
     projection, positional conv (weight-normed: w = g v / ||v|| per tap, undone here; five plain convs for data2vec), encoder."""
