@@ -175,6 +175,26 @@ class CapturedStep:
     def __init__(self, rows: int, device, k_split: int, ksplit_min_k: int) -> None:
         self.launches, self._keep, self._ks_cnts, self._graph = [], [], [], None
         self._n_rows, self._device, self._k_split, self._ksplit_min_k = rows, device, k_split, ksplit_min_k
+        self._model, self._model_sig = None, None
+
+    def watch(self, model) -> None:
+        """Record the signature of every parameter and buffer of ``model`` (transformer.state_signature): the plan points into
+        them and into values derived from them, and cannot be rebuilt in place."""
+        from ..transformer import state_signature
+
+        self._model, self._model_sig = model, state_signature(model)
+
+    def check_model(self) -> None:
+        """RuntimeError when a parameter or buffer of the watched model changed since the plan was built: its launches would read
+        the new values of the tensors they use directly and the old values of everything derived - a mixture of two checkpoints."""
+        if self._model is None:
+            return
+        from ..transformer import state_signature
+
+        if state_signature(self._model) != self._model_sig:
+            raise RuntimeError(f"{type(self).__name__}: the model's parameters changed since this decoder was built (in-place update, "
+                               "load_state_dict or .to()); its launch plan holds raw pointers into the old derived weights and "
+                               "cannot be rebuilt in place - build a new decoder")
 
     def add(self, fn, *args) -> None:
         self.launches.append((fn, args))
@@ -224,6 +244,7 @@ class CapturedStep:
 
     def begin(self, graph: bool):
         """the head of a run: warm up once eagerly, synchronise and capture once (``graph``), reset; returns the call that runs a step"""
+        self.check_model()
         if graph and self._graph is None:
             self.reset()
             self.step()  # eager warm-up: loads every kernel before the capture

@@ -119,6 +119,7 @@ class GreedyDecoder(plan.CapturedStep):
         # plain projections with a long K (fc2: K = 4 d) are split over workgroups along K: see pm_dec_linear_ksplit
         super().__init__(self.B, self._E.device, k_split=int(os.environ.get("PM_DEC_KSPLIT", "4")),
                          ksplit_min_k=int(os.environ.get("PM_DEC_KSPLIT_MINK", "1024")))
+        self.watch(dec)  # rebind() / run() refuse to go on once a parameter or buffer of the decoder changed
         self._allocate(dec, memory, prompt, margins)
         for layer in dec.layers:
             if not layer.pre_norm:
@@ -576,7 +577,9 @@ class GreedyDecoder(plan.CapturedStep):
     def rebind(self, memory: Tensor, prompt: Tensor, lengths=None) -> None:
         """New clips, same geometry: re-project the cross K/V INTO the existing buffers and swap the prompt, so the
         captured graph (which holds raw pointers) stays valid.  A decoder built with ``lengths`` takes new ones here (each at
-        most the longest it was built for): key_start is rewritten in place, the same graph serves them."""
+        most the longest it was built for): key_start is rewritten in place, the same graph serves them.  RuntimeError once the
+        decoder's parameters changed (CapturedStep.check_model): the plan points into the old derived weights - build a new one."""
+        self.check_model()
         assert (self.clips, self._P_in) == tuple(prompt.shape)
         if self._ragged != (lengths is not None):
             raise ValueError("greedy decode: rebind() takes lengths= exactly when the decoder was built with lengths=")

@@ -13,7 +13,7 @@ from torch import Tensor, nn
 from .. import _cpu
 from .._hip import ops
 from ..audio.spectrogram import MelSpectrogram
-from ..transformer import Decoder, Encoder, LayerNorm, _f32, _wb, derived
+from ..transformer import Decoder, Encoder, LayerNorm, _f32, _wb, clear_derived, derived
 
 _SIZES = {  # tag -> (n_layers, d_model); "base" is 8 layers exactly as the reference builds it
     "tiny": (4, 384), "tiny.en": (4, 384), "base": (8, 512), "base.en": (8, 512),
@@ -270,8 +270,7 @@ class Whisper(nn.Module):
         params = list(self.parameters()) + list(self.buffers())
         def build():
             twin = copy.deepcopy(self).float()
-            for m in twin.modules():  # the twin derives its own packed / re-typed weights
-                m.__dict__.pop("_pm_derived", None)
+            clear_derived(twin)  # the twin derives its own packed / re-typed weights
             return twin
 
         return derived(self, "exact32", params, build)

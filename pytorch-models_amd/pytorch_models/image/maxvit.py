@@ -122,7 +122,7 @@ class MBConv(nn.Module):
         s1, t1 = _bn_fold(ebn)
         s2, t2 = _bn_fold(dbn)
         sc_conv = self.shortcut[-1] if len(self.shortcut) and isinstance(self.shortcut[-1], nn.Conv2d) else None
-        params = (econv.weight, a, b, s1, t1, dconv.weight, se[1].weight, se[1].bias, se[3].weight, se[3].bias, shrink.weight,
+        params = (econv.weight, a, b, s1, t1, s2, t2, dconv.weight, se[1].weight, se[1].bias, se[3].weight, se[3].bias, shrink.weight,
                   shrink.bias) + ((sc_conv.weight, sc_conv.bias) if sc_conv is not None else ())
 
         def build():

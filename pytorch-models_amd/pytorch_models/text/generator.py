@@ -44,7 +44,7 @@ class DecoderGenerator:
                                       "with generate(): GPT-2); this model decodes token by token: prefill=False")
         if topk == 1 and hasattr(self.model, "token_embs") and hasattr(self.model, "pos_embs"):
             from ..audio2text.generate import greedy_exact
-            from ..transformer import derived
+            from ..transformer import clear_derived, derived
 
             m32 = self.model
             if p0.dtype != torch.float32:  # fp32 twin of a bf16 post-norm model (same values), rebuilt when a parameter changes
@@ -52,11 +52,10 @@ class DecoderGenerator:
 
                 def build():
                     twin = copy.deepcopy(self.model).float()
-                    for mod in twin.modules():
-                        mod.__dict__.pop("_pm_derived", None)
+                    clear_derived(twin)
                     return twin
 
-                m32 = derived(self.model, "exact32", list(self.model.parameters()), build)
+                m32 = derived(self.model, "exact32", list(self.model.parameters()) + list(self.model.buffers()), build)
             out = greedy_exact(m32, None, torch.tensor([tokens], device=device), min(max_tokens, room))[0].tolist()
             new = out[n:]
             if eos_token_id is not None and eos_token_id in new:

@@ -221,7 +221,10 @@ class T5DecodeState(plan.CapturedStep):
 
 
 def _signature(model) -> tuple:
-    return tuple((p.data_ptr(), p._version) for p in model.parameters())
+    """every parameter and buffer, with the fields derived() keys on: a dtype or device change separates two states too"""
+    from ..transformer import state_signature
+
+    return state_signature(model)
 
 
 @torch.no_grad()

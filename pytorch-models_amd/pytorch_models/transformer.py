@@ -43,15 +43,33 @@ def _sig(ts) -> tuple:
     return tuple((t.data_ptr(), 0 if t.is_inference() else t._version, t.dtype, t.device) for t in ts if t is not None)
 
 
+def _same_objects(kept: tuple, params) -> bool:
+    i = 0
+    for p in params:
+        if p is None:
+            continue
+        if i >= len(kept) or kept[i] is not p:
+            return False
+        i += 1
+    return i == len(kept)
+
+
 def derived(module: nn.Module, key: str, params, build):
     """Value derived from parameters (packed / re-typed weights), rebuilt when any of them changes
-    (in-place ``copy_`` bumps ``_version``; ``.to()`` moves storage)."""
+    (in-place ``copy_`` bumps ``_version``; ``.to()`` moves storage).  The entry also keeps the dependencies themselves and
+    compares them by identity: ``module.cpu()`` / ``.cuda()`` replace a BUFFER by a new tensor whose version counter starts
+    again, and the allocator likes to hand its old address back - (address, version, dtype, device) then repeats with other
+    values behind it (the STFT window after .cpu(), an update, .cuda()).  A kept tensor cannot lend its address or its id.
+    The price: a replaced device buffer stays allocated until the next call with this key drops the entry (clear_derived
+    drops all of them).  Pass the dependencies as the objects the module holds - a fresh view or slice on every call never
+    matches and would rebuild every time (tests/test_hip_coherence.py asserts that a second warm run rebuilds nothing)."""
     store = module.__dict__.setdefault("_pm_derived", {})
+    params = tuple(params)  # read three times below: an iterator would be spent after the first
     sig = _sig(params)
     hit = store.get(key)
-    if hit is None or hit[0] != sig:
+    if hit is None or hit[0] != sig or not _same_objects(hit[2], params):
         with torch.no_grad():
-            hit = (sig, build())
+            hit = (sig, build(), tuple(p for p in params if p is not None))
         store[key] = hit
         # A derived tensor is built by kernels on whatever stream is current and then used from ANY stream (Encoder.forward
         # runs the halves of a large batch on two): wait for the build once, here, instead of ordering every later use.
@@ -60,6 +78,40 @@ def derived(module: nn.Module, key: str, params, build):
                 not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream().synchronize()
     return hit[1]
+
+
+_CACHES = ("_pm_derived", "_pm_tables", "_pm_buckets", "_pm_t5_decode", "_pm_out_shape")
+
+
+def clear_derived(module: nn.Module) -> None:
+    """Drop every lazily built cache of ``module`` and its submodules (derived weights, position tables, bucket tables, the
+    kept T5 decode state); the next call rebuilds them from the parameters as they are now.  The call to make after a write
+    the signature of derived() cannot see: ``p.data.copy_(...)`` (no ``_version`` bump) and in-place writes to parameters
+    created under torch.inference_mode() (no version counter).  Objects that hold raw pointers into the old values
+    (GraphedForward, GreedyDecoder / BeamDecoder) are not reachable from here: build new ones."""
+    for m in module.modules():
+        for name in _CACHES:
+            m.__dict__.pop(name, None)
+
+
+class StateSignature:
+    """The state of every parameter and buffer of a module at one moment: what the holders of raw pointers (GraphedForward, the
+    decoders, T5's kept decode state) record when they are built and compare before they run.  The fields of _sig plus the
+    tensors themselves, kept and compared by identity as derived() does (a replaced buffer may repeat the other four)."""
+
+    def __init__(self, module: nn.Module) -> None:
+        self.tensors = tuple(module.parameters()) + tuple(module.buffers())
+        self.sig = _sig(self.tensors)
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, StateSignature) and self.sig == other.sig and len(self.tensors) == len(other.tensors)
+                and all(a is b for a, b in zip(self.tensors, other.tensors)))
+
+    __hash__ = None
+
+
+def state_signature(module: nn.Module) -> StateSignature:
+    return StateSignature(module)
 
 
 def _f32(module: nn.Module, key: str, t: Tensor | None) -> Tensor | None:
@@ -204,7 +256,11 @@ class MHA(nn.Module):
         """q/k/v projection with ``norm`` folded in: (w' = bf16(gamma (.) w), s[n] = sum_k w'[n][k],
         c[n] = b[n] + sum_k beta[k] w[n][k]) so that proj(norm(x)) = rstd * (x w'^T - mean * s) + c."""
         w, b = self._pack("qkv")
-        return derived(self, "pack_qkv_ln", (w, b, norm.weight, norm.bias), lambda: _fold_ln(w, b, norm))
+        # keyed on the parameters, not on (w, b): _pack also rebuilds on calls that never come here (the unfolded path at a
+        # small M), and a later rebuild can land on the address this signature last saw
+        mods = (self.q_proj, self.k_proj, self.v_proj)
+        params = [m.weight for m in mods] + [m.bias for m in mods] + [norm.weight, norm.bias]
+        return derived(self, "pack_qkv_ln", params, lambda: _fold_ln(w, b, norm))
 
     def _pack_cls(self, norm: "LayerNorm"):
         """k / v projections with ``norm`` folded in, per head, for a single query (EncoderLayer.forward_first_row):
