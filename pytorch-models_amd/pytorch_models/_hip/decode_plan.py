@@ -29,6 +29,14 @@ def _ld(t: Tensor | None) -> int:
 
 
 # ---- argument builders: tensors and named options in, the positional tuple of the C entry point out (stream slot = None) ----
+def _unit_rows(what: str, *ts: Tensor | None) -> None:
+    """The builders pass a row stride and a pointer per matrix: the columns must be one element apart.  Checked where a plan is
+    BUILT (attribute reads); a built plan holds integers and is not looked at again."""
+    for t in ts:
+        if t is not None and t.dim() >= 1 and t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{what}: operand rows must have unit column stride, got strides {tuple(t.stride())}")
+
+
 def linear_args(x: Tensor, w: Tensor, out: Tensor | None, rows: int, *, ln=None, bias=None, resid=None, act: int = 0, mode: int = 0,
                 cache=(None, None), geom=(0, 0, 0), pos=None, argmax_ws=(None, None)) -> tuple:
     """pm_dec_linear: act(LN?(x) w^T + bias) + resid.  mode 0 stores to ``out``; mode 1 ([q|k|v]) stores q to ``out`` and k, v into
@@ -36,6 +44,7 @@ def linear_args(x: Tensor, w: Tensor, out: Tensor | None, rows: int, *, ln=None,
     (max, index) pairs to ``argmax_ws`` = (ws_val, ws_idx).  ``ln`` = (gamma, beta, eps) or None."""
     N, K = w.shape
     g, b, eps = ln if ln is not None else (None, None, 0.0)
+    _unit_rows("linear_args", x, w, resid, out, g, b, bias)
     return (x.data_ptr(), x.stride(0), ptr(g), ptr(b), float(eps), w.data_ptr(), w.stride(0), ptr(bias), ptr(resid), _ld(resid),
             ptr(out), _ld(out), rows, N, K, act, mode, ptr(cache[0]), ptr(cache[1]), *geom, ptr(pos), ptr(argmax_ws[0]),
             ptr(argmax_ws[1]), None)
@@ -55,6 +64,7 @@ def ksplit_args(x: Tensor, w: Tensor, out: Tensor, rows: int, k_split: int, ws: 
                 act: int = 0) -> tuple:
     """pm_dec_linear_ksplit: linear_args' mode 0 without LayerNorm, K split over ``k_split`` workgroups per feature tile"""
     N, K = w.shape
+    _unit_rows("ksplit_args", x, w, resid, out, bias)
     return (x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), ptr(bias), ptr(resid), _ld(resid), out.data_ptr(), out.stride(0),
             rows, N, K, act, k_split, ws.data_ptr(), tickets.data_ptr(), None)
 
@@ -62,6 +72,7 @@ def ksplit_args(x: Tensor, w: Tensor, out: Tensor, rows: int, k_split: int, ws: 
 def kparts_args(x: Tensor, w: Tensor, parts: Tensor, rows: int, k_split: int) -> tuple:
     """pm_dec_linear_kparts: the K parts of x w^T left as parts in ``parts`` (>= k_split, rows, N) for the next chain block to add"""
     N, K = w.shape
+    _unit_rows("kparts_args", x, w, parts)
     return (x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), parts.data_ptr(), parts.stride(1), parts.stride(0), rows, N, K,
             k_split, None)
 
@@ -72,6 +83,9 @@ KV = namedtuple("KV", "k v stride_b stride_h stride_k")
 
 def cache_kv(kc: Tensor, vc: Tensor) -> KV:
     """self-attention caches (rows, heads, t_max, 64)"""
+    _unit_rows("cache_kv", kc, vc)
+    if kc.shape != vc.shape or any(a != b for n, a, b in zip(kc.shape, kc.stride(), vc.stride()) if n > 1):
+        raise ValueError(f"cache_kv: k and v caches must share one layout, got strides {tuple(kc.stride())} and {tuple(vc.stride())}")
     return KV(kc.data_ptr(), vc.data_ptr(), kc.stride(0), kc.stride(1), kc.stride(2))
 
 

@@ -87,12 +87,29 @@ def _cuda(*ts: Tensor) -> None:
     check_devices(*ts)
 
 
+def _apart(t: Tensor) -> bool:
+    """No two elements of ``t`` share an address (strides read only): what a tensor the kernel WRITES through its strides must
+    satisfy - a stride-0 broadcast or overlapping rows would be written by several workgroups at once.  Caller-supplied
+    tensors only; the ones a wrapper allocates are contiguous."""
+    if t.is_contiguous():
+        return True
+    ext = 1
+    for s, n in sorted((s, n) for n, s in zip(t.shape, t.stride()) if n > 1):
+        if s < ext:
+            return False
+        ext += (n - 1) * s
+    return True
+
+
 def linear_ln_supported(M: int, N: int, K: int, act: str, produce: bool) -> bool:
     return bool(lib().pm_linear_ln_supported(M, N, K, ACT[act], int(produce)))
 
 
 def ln_stats_finalize(partials: Tensor, N: int, eps: float) -> Tensor:
     """(M, N/64, 2) row partials [sum, sum of squares] -> (M, 2) [mean, rstd]."""
+    _cuda(partials)
+    _need(partials.dim() == 3 and partials.dtype == torch.float32 and partials.is_contiguous() and N % 64 == 0
+          and partials.shape[1:] == (N // 64, 2), "ln_stats_finalize: partials must be contiguous f32 (M, N / 64, 2)")
     M = partials.shape[0]
     stats = torch.empty((M, 2), dtype=torch.float32, device=partials.device)
     rc = _launch("ln_stats_finalize", float(partials.numel() * 4), lambda: lib().pm_ln_stats_finalize(
@@ -144,7 +161,7 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
     resid_period = P > 0, (P, N): row m adds resid[m % P] (a position table broadcast over the batch).
     LayerNorm fold (pm_linear_bf16_ln): ln_stats (M, 2) + ln_s (N) normalise the input rows in the epilogue;
     want_row_stats=True additionally returns the (M, N/64, 2) partial statistics of the output rows."""
-    _cuda(x, w, bias, resid, out)
+    _cuda(x, w, bias, resid, out, ln_stats, ln_s)
     args, out, rows = _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period)
     M, N, K = args[14:17]
     rc = _launch("linear_bf16", (2.0 * M * N * K, _linear_bytes(x, w, out, resid)), lambda: lib().pm_linear_bf16_ws(*args, _stream()))
@@ -163,6 +180,8 @@ def _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_ro
         _need(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N, "linear: bias must be f32 (N)")
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype, device=x.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("linear: rows of out overlap")
     _need(out.shape == (M, N) and out.stride(1) == 1, "linear: bad out")
     if resid is not None:
         _need(resid_period >= 0 and resid.shape == (resid_period or M, N) and resid.stride(1) == 1,
@@ -215,6 +234,8 @@ def linear_f32(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "
               and resid.shape[0] >= (resid_period or M), "linear_f32: resid must be f32 (rows, N)")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=w.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("linear_f32: rows of out overlap")
     _need(out.dtype == torch.float32 and out.shape == (M, N) and out.stride(1) == 1, "linear_f32: bad out")
     rc = _launch("linear_f32", 2.0 * M * N * K, lambda: lib().pm_linear_f32(
         x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
@@ -259,12 +280,14 @@ def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, 
     M, d = x.shape
     _need((gamma is None) == (beta is None), "layernorm: gamma and beta come together")
     if gamma is not None:
-        _need(gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == d and beta.numel() == d,
-              "layernorm: gamma / beta must be f32 (d)")
+        _need(gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == d and beta.numel() == d
+              and gamma.is_contiguous() and beta.is_contiguous(), "layernorm: gamma / beta must be contiguous f32 (d)")
     if resid is not None:
         _need(resid.shape == x.shape and resid.stride(1) == 1, "layernorm: resid must be (M, d), row-major")
     if out is None:
         out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("layernorm: rows of out overlap")
     _need(out.shape == (M, d) and out.stride(1) == 1, "layernorm: out must be (M, d), row-major")
     gp, bp = (gamma.data_ptr(), beta.data_ptr()) if gamma is not None else (None, None)
     nbytes = float(M * d * (x.element_size() + out.element_size() + (resid.element_size() if resid is not None else 0)))
@@ -285,7 +308,7 @@ def rmsnorm(x: Tensor, gamma: Tensor, eps: float, out_dtype: torch.dtype | None 
     _cuda(x, gamma)
     _need(x.dim() == 2 and x.stride(1) == 1, "rmsnorm: x must be (M, d), row-major")
     M, d = x.shape
-    _need(gamma.dtype == torch.float32 and gamma.numel() == d, "rmsnorm: gamma must be f32 (d)")
+    _need(gamma.dtype == torch.float32 and gamma.numel() == d and gamma.is_contiguous(), "rmsnorm: gamma must be contiguous f32 (d)")
     out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
     rc = _launch("layernorm", float(M * d * (x.element_size() + out.element_size())), lambda: lib().pm_rmsnorm(
         x.data_ptr(), x.stride(0), _dt(x), gamma.data_ptr(), float(eps), out.data_ptr(), out.stride(0), _dt(out), M, d, _stream()))
@@ -321,6 +344,8 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
         _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention: bf16 operands with unit last stride")
     if out is None:
         out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("attention: rows of out overlap")
     _need(out.shape == (B, Lq, D) and out.dtype == torch.bfloat16 and out.stride(2) == 1, "attention: out must be bf16 (B, Lq, H*hd)")
     args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
             v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, int(causal))
@@ -353,7 +378,8 @@ def conv2d_nhwc(x: Tensor, w: Tensor, bias: Tensor | None, stride: int = 1, pad:
     N, H, W, Cin = x.shape
     Cout, kh, kw, cg = w.shape
     _need(Cin % groups == 0 and Cout % groups == 0 and cg == Cin // groups, "conv2d_nhwc: channel / group mismatch")
-    _need(bias is None or (bias.dtype == torch.float32 and bias.numel() == Cout), "conv2d_nhwc: bias must be f32 (Cout)")
+    _need(bias is None or (bias.dtype == torch.float32 and bias.numel() == Cout and bias.is_contiguous()),
+          "conv2d_nhwc: bias must be contiguous f32 (Cout)")
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
     _need(resid is None or (resid.shape == out.shape and resid.dtype == torch.bfloat16 and resid.is_contiguous()), "conv2d_nhwc: resid must match the output")
@@ -410,7 +436,7 @@ def linear_strided(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_batch
     """pm_linear_bf16_ex: row m of the A operand is the K contiguous bf16 values at
     x.flat[(m // rows_per_batch) * batch_stride + (m % rows_per_batch) * row_stride : ... + K] (rows may overlap:
     that is how a strided conv window is expressed); resid rows repeat every resid_period rows."""
-    _cuda(x, w, bias, resid)
+    _cuda(x, w, bias, resid, out)
     args, out = _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out)
     N = w.shape[0]
     rc = _launch("linear_bf16", 2.0 * M * N * K, lambda: lib().pm_linear_bf16_ws(*args, _stream()))
@@ -435,8 +461,8 @@ def _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, b
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype, device=x.device)
     else:  # e.g. a column slice of a wider matrix (one group of a grouped conv)
-        _need(out.shape == (M, N) and out.stride(1) == 1 and (out.is_cuda or not x.is_cuda),
-              "linear_strided: out must be (M, N) with unit column stride")
+        _need(out.shape == (M, N) and out.stride(1) == 1 and (out.is_cuda or not x.is_cuda) and _apart(out),
+              "linear_strided: out must be (M, N) with unit column stride and rows that do not overlap")
     ws, ws_bytes = _ws_args(M, out.device) if out.is_cuda else (None, 0)
     args = (x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0),
             bias.data_ptr() if bias is not None else None, resid.data_ptr() if resid is not None else None,
@@ -583,14 +609,19 @@ def mel_csr(filters: Tensor) -> tuple[Tensor, Tensor, Tensor]:
 def stft_mel(x: Tensor, tables, n_fft: int, hop: int, n_frames: int, mode: int, csr=None, n_mels: int = 0) -> Tensor:
     """x (..., T) f32 -> mode 0: (..., n_fft/2+1, n_frames) power; 1: (..., n_mels, n_frames) mel power;
     2: Whisper log-mel (log10, per-clip max - 8 floor, (x + 4) / 4) via pm_stft_mel + pm_logmel_finalize."""
-    _cuda(x, tables[0])
+    ptr, col, val = csr if csr is not None else (None, None, None)
+    _cuda(x, tables[0], tables[1], ptr, col, val)
+    _need(all(t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() for t in tables[:2]) and tables[0].shape == tables[1].shape,
+          "stft_mel: tables must be stft_tables' two contiguous f32 vectors")
+    _need(csr is None or (ptr.dtype == torch.int32 and col.dtype == torch.int32 and val.dtype == torch.float32 and ptr.shape == (n_mels + 1,)
+                          and col.dim() == 1 and val.shape == col.shape and ptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()),
+          "stft_mel: csr must be mel_csr's contiguous (int32 (n_mels + 1), int32 (nnz), f32 (nnz))")
     lead, T = x.shape[:-1], x.shape[-1]
     x2 = x.reshape(-1, T).float().contiguous()
     B = x2.shape[0]
     rows = n_fft // 2 + 1 if mode == 0 else n_mels
     out = torch.empty((B, rows, n_frames), dtype=torch.float32, device=x.device)
     peak = torch.empty(max(B, 1), dtype=torch.int32, device=x.device) if mode == 2 else None
-    ptr, col, val = csr if csr is not None else (None, None, None)
     fn = lib().pm_stft_mel_folded if len(tables) > 2 and tables[2] else lib().pm_stft_mel
     rc = _launch("stft_mel", float(x2.numel() * 4 + out.numel() * 4), lambda: fn(
         x2.data_ptr(), T, B, T, tables[0].data_ptr(), tables[1].data_ptr(), n_fft, hop, n_frames, mode,
@@ -612,7 +643,7 @@ def whisper_stem1(x: Tensor, w1: Tensor, b1: Tensor) -> Tensor:
     B, C, T = x.shape
     d, K = w1.shape
     _need(w1.dtype == torch.bfloat16 and w1.is_contiguous() and K % 3 == 0 and K // 3 >= C, "whisper_stem1: bad packed weight")
-    _need(b1.dtype == torch.float32 and b1.numel() == d, "whisper_stem1: bias f32 (d)")
+    _need(b1.dtype == torch.float32 and b1.numel() == d and b1.is_contiguous(), "whisper_stem1: bias must be contiguous f32 (d)")
     out = torch.empty((B, T + 2, d), dtype=torch.bfloat16, device=x.device)
     rc = _launch("whisper_stem1", float(x.numel() * 4 + out.numel() * 2), lambda: lib().pm_whisper_stem1(
         x.data_ptr(), w1.data_ptr(), b1.data_ptr(), out.data_ptr(), B, C, K // 3, T, d, _stream()))
@@ -663,13 +694,28 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
 
 # ---- decode-step kernels as standalone ops (the decoders build their launch lists in decode_plan.py, whose argument builders
 # these wrappers share; the wrappers serve tests) ----
+def _dec_rows(who: str, x: Tensor, w: Tensor, bias: Tensor | None, resid: Tensor | None, ln: tuple | None) -> tuple[int, int, int]:
+    """The operands of the pm_dec_linear family, whose argument builders (decode_plan.linear_args / ksplit_args) pass row strides
+    and raw pointers only: f32 x (M, K) and bf16 w (N, K) rows with unit column stride, f32 bias (N), f32 resid (M, N) rows,
+    ln = (gamma, beta, eps) with f32 (K) vectors.  Returns (M, N, K)."""
+    _need(x.dim() == 2 and w.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.bfloat16 and x.shape[1] == w.shape[1]
+          and x.stride(1) == 1 and w.stride(1) == 1, f"{who}: f32 x (M, K) and bf16 w (N, K) rows with unit column stride")
+    M, K = x.shape
+    N = w.shape[0]
+    _need(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N), f"{who}: bias must be contiguous f32 (N)")
+    _need(resid is None or (resid.dtype == torch.float32 and resid.shape == (M, N) and resid.stride(1) == 1),
+          f"{who}: resid must be f32 (M, N) rows with unit column stride")
+    if ln is not None:
+        _need(all(isinstance(t, Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == K for t in ln[:2]),
+              f"{who}: ln must be (gamma, beta, eps) with contiguous f32 (K) vectors")
+    return M, N, K
+
+
 def dec_linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, ln: tuple | None = None, act: str = "none",
                resid: Tensor | None = None) -> Tensor:
     """y = act(LN?(x) @ w.T + bias) + resid for <= 64 rows of f32 x and bf16 w (fp32-exact: bf16x3 split)."""
-    _cuda(x, w, bias, resid)
-    _need(x.dtype == torch.float32 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2, "dec_linear: f32 x, bf16 w")
-    M, K = x.shape
-    N = w.shape[0]
+    _cuda(x, w, bias, resid, *(ln[:2] if ln is not None else ()))
+    M, N, K = _dec_rows("dec_linear", x, w, bias, resid, ln)
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     plan.call(lib().pm_dec_linear, plan.linear_args(x, w, out, M, ln=ln, bias=bias, resid=resid, act=ACT[act]), _stream(),
               f"pm_dec_linear(M={M}, N={N}, K={K})")
@@ -680,9 +726,7 @@ def dec_linear_ksplit(x: Tensor, w: Tensor, bias: Tensor | None = None, *, k_spl
                       resid: Tensor | None = None) -> Tensor:
     """dec_linear without LayerNorm, K split over k_split workgroups per 16-feature tile (pm_dec_linear_ksplit)."""
     _cuda(x, w, bias, resid)
-    _need(x.dtype == torch.float32 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2, "dec_linear_ksplit: f32 x, bf16 w")
-    M, K = x.shape
-    N = w.shape[0]
+    M, N, K = _dec_rows("dec_linear_ksplit", x, w, bias, resid, None)
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     ws, cnt = plan.ksplit_workspace(M, N, k_split, x.device)
     plan.call(lib().pm_dec_linear_ksplit, plan.ksplit_args(x, w, out, M, k_split, ws, cnt, bias=bias, resid=resid, act=ACT[act]),
@@ -693,8 +737,9 @@ def dec_linear_ksplit(x: Tensor, w: Tensor, bias: Tensor | None = None, *, k_spl
 
 def dec_argmax(x: Tensor, w: Tensor, ln: tuple) -> tuple[Tensor, Tensor]:
     """Per-row argmax (and max) of LN(x) @ w.T without materialising the logits."""
-    M, K = x.shape
-    N = w.shape[0]
+    _need(isinstance(ln, tuple) and len(ln) == 3, "dec_argmax: ln must be (gamma, beta, eps)")
+    _cuda(x, w, *ln[:2])
+    M, N, K = _dec_rows("dec_argmax", x, w, None, None, ln)
     tile = lib().pm_dec_argmax_tile(K)
     nt = (N + tile - 1) // tile
     wv = torch.empty(M, nt, dtype=torch.float32, device=x.device)
@@ -722,10 +767,21 @@ def dec_linear_plan(M: int, N: int, K: int, *, ln: bool = False, mode: int = 0, 
     return out
 
 
+def _dec_qkv(who: str, q: Tensor, k: Tensor, v: Tensor) -> tuple[int, int, int]:
+    """q contiguous f32 (B, H*64); k, v bf16 (B, H, T, 64) caches of one layout with unit last stride (decode_plan.cache_kv passes
+    the three leading strides of k for both).  Returns (B, H, T)."""
+    _need(k.dim() == 4 and k.shape[3] == 64 and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16 and v.shape == k.shape
+          and v.stride() == k.stride() and k.stride(3) == 1, f"{who}: k / v must be bf16 (B, H, T, 64) caches with one layout and unit last stride")
+    B, H, T, _ = k.shape
+    _need(q.dtype == torch.float32 and q.shape == (B, H * 64) and q.is_contiguous(), f"{who}: q must be contiguous f32 (B, H*64)")
+    return B, H, T
+
+
 def dec_attention(q: Tensor, k: Tensor, v: Tensor, lk: int) -> Tensor:
     """q f32 (B, H*64); k, v bf16 (B, H, T, 64) caches; attends over the first lk keys."""
     _cuda(q, k, v)
-    B, H, T, _ = k.shape
+    B, H, T = _dec_qkv("dec_attention", q, k, v)
+    _need(1 <= lk <= T, "dec_attention: 1 <= lk <= cache length")
     out = torch.empty_like(q)
     plan.call(lib().pm_dec_attention, plan.attention_args(q, plan.cache_kv(k, v), out, B, H, pos=None, lk_add=lk, lk_max=T), _stream())
     return out
@@ -747,6 +803,9 @@ def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("prefill_attention: rows of out overlap")
+    _need(_apart(kc) and _apart(vc), "prefill_attention: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention: out must be bf16 (B * C, H * 64)")
     kv = plan.cache_kv(kc, vc)
     rc = _launch("prefill_attention", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_bf16(
@@ -764,7 +823,7 @@ def _key_start(key_start: Tensor, B: int, what: str) -> None:
 def dec_attention_ragged(q: Tensor, k: Tensor, v: Tensor, lk: int, key_start: Tensor) -> Tensor:
     """dec_attention over keys min(key_start[b], lk - 1) .. lk - 1 of row b (pm_dec_attention_ragged)."""
     _cuda(q, k, v, key_start)
-    B, H, T, _ = k.shape
+    B, H, T = _dec_qkv("dec_attention_ragged", q, k, v)
     _key_start(key_start, B, "dec_attention_ragged")
     _need(1 <= lk <= T, "dec_attention_ragged: 1 <= lk <= cache length")
     out = torch.empty_like(q)
@@ -789,6 +848,9 @@ def prefill_attention_ragged(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, 
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention_ragged: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("prefill_attention_ragged: rows of out overlap")
+    _need(_apart(kc) and _apart(vc), "prefill_attention_ragged: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention_ragged: out must be bf16 (B * C, H * 64)")
     kv = plan.cache_kv(kc, vc)
     rc = _launch("prefill_attention_ragged", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_ragged_bf16(
@@ -825,6 +887,9 @@ def embed_tokens_ragged(tokens: Tensor, emb: Tensor, pos: Tensor, key_start: Ten
 def dec_embed_ragged(tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, pos: Tensor, key_start: Tensor) -> Tensor:
     """x (B, d) f32: emb[tok_cur[b]] + pos_tab[max(0, pos - key_start[b])]; pos = the int32 (1,) device position."""
     _cuda(tok_cur, emb, pos_tab, pos, key_start)
+    _need(tok_cur.dim() == 1 and tok_cur.is_contiguous() and emb.dim() == 2 and emb.is_contiguous() and pos_tab.dim() == 2
+          and pos_tab.is_contiguous() and pos_tab.shape[1] == emb.shape[1] and pos.numel() == 1,
+          "dec_embed_ragged: contiguous tok_cur (B,), emb (V, d), pos_tab (rows, d); pos is one device int32")
     B = tok_cur.shape[0]
     _key_start(key_start, B, "dec_embed_ragged")
     _need(emb.dtype == torch.bfloat16 and pos_tab.dtype == torch.float32 and pos.dtype == torch.int32 and tok_cur.dtype == torch.int64,
@@ -839,8 +904,8 @@ def _tail_state(what: str, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens:
     B = prompt.shape[0]
     _need(pos.dtype == torch.int32 and ticket.dtype == torch.int32 and pos.numel() == 1 and ticket.numel() == 1, f"{what}: int32 position and ticket")
     _need(prompt.dtype == torch.int64 and prompt.is_contiguous() and tokens.dtype == torch.int64 and tokens.is_contiguous()
-          and tokens.shape[0] == B and tokens.shape[1] >= prompt.shape[1] and tok_cur.dtype == torch.int64 and tok_cur.shape == (B,),
-          f"{what}: int64 prompt (B, P), tokens (B, Ttot >= P), tok_cur (B,)")
+          and tokens.shape[0] == B and tokens.shape[1] >= prompt.shape[1] and tok_cur.dtype == torch.int64 and tok_cur.shape == (B,) and tok_cur.is_contiguous(),
+          f"{what}: contiguous int64 prompt (B, P), tokens (B, Ttot >= P), tok_cur (B,)")
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
           and pos_tab.shape[1] == emb.shape[1] and 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: bf16 table, f32 positions covering position + 1")
 
@@ -897,7 +962,8 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
     """pm_dec_whisper_rules as a standalone op (the generator puts it into its launch list): filters logits (B, V) f32 IN PLACE for
     the token at index pos + 1 of tokens (B, Ttot) int64; returns logits."""
     _cuda(logits, tokens, pos)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1, "dec_whisper_rules: logits f32 (B, V)")
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and _apart(logits),
+          "dec_whisper_rules: logits f32 (B, V) rows that do not overlap")
     _need(tokens.dim() == 2 and tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.shape[0] == logits.shape[0],
           "dec_whisper_rules: tokens int64 (B, Ttot)")
     _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_whisper_rules: pos is one device int32")
@@ -954,7 +1020,7 @@ def dec_beam_select(cand_score: Tensor, cand_tok: Tensor, scores: Tensor, finish
           "dec_beam_select: candidates (B * W, W) f32 / int32")
     _need(tokens.dim() == 2 and tokens.shape[0] == R and tokens.dtype == torch.int64 and tokens.is_contiguous()
           and prompt.dim() == 2 and prompt.shape[0] == R and prompt.dtype == torch.int64 and prompt.is_contiguous()
-          and tokens.shape[1] >= prompt.shape[1] and tok_cur.shape == (R,) and tok_cur.dtype == torch.int64,
+          and tokens.shape[1] >= prompt.shape[1] and tok_cur.shape == (R,) and tok_cur.dtype == torch.int64 and tok_cur.is_contiguous(),
           "dec_beam_select: tokens (B * W, Ttot), prompt (B * W, P), tok_cur (B * W) int64")
     V, d = emb.shape
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
@@ -1095,6 +1161,8 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, N: int, H: int, W: int, n_
               f"window_attention: bias must be contiguous f32 ({n_heads}, {L}, {L})")
     if out is None:
         out = torch.empty((M, D), dtype=torch.bfloat16, device=q.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("window_attention: rows of out overlap")
     _need(out.dtype == torch.bfloat16 and out.shape[0] == M and out.shape[1] >= D and out.stride(1) == 1, "window_attention: bad out")
     nbytes = float(M * D * 2 * 4)
     rc = _launch("window_attention", (4.0 * M * L * D, nbytes), lambda: lib().pm_window_attention_bf16(
@@ -1533,6 +1601,7 @@ def cls_head_gemm(x: Tensor, w: Tensor, bias: Tensor | None = None) -> Tensor:
     G, N, K = w.shape
     _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.is_contiguous(), "cls_head_gemm: bf16 x, contiguous bf16 w (G, N, K)")
     M = x.shape[0]
+    _need(x.shape[1:] in ((G, K), (G * K,)), "cls_head_gemm: x must be (M, G, K) or (M, G * K) for w (G, N, K)")
     x2 = x.reshape(M, G * K)
     _need(x2.stride(1) == 1, "cls_head_gemm: x rows must be contiguous")
     if bias is not None:
@@ -1656,6 +1725,7 @@ def align_lse(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tens
     head indices, lengths / frames int32 (B), all on the device -> lse f32 (B, n, L): log sum_{f < F_b} exp(q_t . k_f / 8) of each
     selected head; rows t >= len_b are not written."""
     B, L, S, H, nh = _align_qk("align_lse", q, k, heads, lengths, frames)
+    _cuda(q, out)
     if out is None:
         out = torch.empty((B, nh, L), dtype=torch.float32, device=q.device)
     _need(out.dtype == torch.float32 and out.shape == (B, nh, L) and out.is_contiguous(), f"align_lse: out must be contiguous f32 {(B, nh, L)}")
@@ -1675,8 +1745,8 @@ def align_matrix(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: T
     _cuda(q, lse, m)
     _need(L <= ALIGN_MAX_ROWS, f"align_matrix: at most {ALIGN_MAX_ROWS} token rows, got {L}")
     _need(lse.dtype == torch.float32 and lse.shape == (B, nh, L) and lse.is_contiguous(), f"align_matrix: lse must be contiguous f32 {(B, nh, L)}")
-    _need(m.dtype == torch.float32 and m.shape == (B, L, S) and m.stride(2) == 1 and m.stride(1) >= S,
-          f"align_matrix: m must be f32 {(B, L, S)} with a unit last stride")
+    _need(m.dtype == torch.float32 and m.shape == (B, L, S) and m.stride(2) == 1 and m.stride(1) >= S and _apart(m),
+          f"align_matrix: m must be f32 {(B, L, S)} with a unit last stride and rows that do not overlap")
     rc = _launch("align_matrix", (2.0 * B * nh * L * S * 64, float(4 * B * L * S)), lambda: lib().pm_align_matrix_bf16(
         q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), heads.data_ptr(), lengths.data_ptr(),
         frames.data_ptr(), lse.data_ptr(), m.data_ptr(), m.stride(1), m.stride(0), B, L, S, nh, H, float(inv_heads), int(bool(first)),
@@ -1779,6 +1849,8 @@ def attention_varlen(q: Tensor, k: Tensor, v: Tensor, n_heads: int, seq: SeqLens
         _need(t.dtype == torch.bfloat16 and t.stride(1) == 1, "attention_varlen: bf16 operands with unit last stride")
     if out is None:
         out = torch.empty((T, D), dtype=torch.bfloat16, device=q.device)
+    elif not (out.is_contiguous() or _apart(out)):
+        raise ValueError("attention_varlen: rows of out overlap")
     _need(out.shape == (T, D) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "attention_varlen: out must be bf16 (T_total, H*64)")
     if T == 0:
         return out
@@ -1862,6 +1934,7 @@ def rows_zero_tail(x: Tensor, seq: SeqLens) -> Tensor:
     """Zeroes rows t >= len_b of a padded (B, L, d) tensor IN PLACE and returns it (pm_rows_zero_tail)."""
     _seq(seq, "rows_zero_tail", x)
     B, L, d = _padded(x, seq, "rows_zero_tail")
+    _need(_apart(x), "rows_zero_tail: rows of x overlap")
     rc = _launch("rows_zero_tail", (0.0, float(B * L - seq.total) * d * x.element_size()), lambda: lib().pm_rows_zero_tail(
         x.data_ptr(), x.stride(0), x.stride(1), seq.cu.data_ptr(), B, L, d, x.element_size(), _stream()))
     check(rc, f"pm_rows_zero_tail(B={B}, L={L}, d={d})")
