@@ -481,6 +481,32 @@ int pm_dec_sample_topk_ragged(const float* logits, int64_t ldl, int64_t V, int64
                               const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d, int32_t* ticket,
                               int64_t B, void* stream);
 
+/* The sampling tail (csrc/sample.hip): pm_dec_sample_topk's place in a step, with a temperature, the whole vocabulary as an
+ * option, a nucleus cut and the emitted token's log-probability.  logits (B, V) f32, row stride ldl, after the rules (finite
+ * or -inf); m = the row maximum.
+ *   logprobs (B, Ttot) f32 or NULL: [b, t + 1] = l[token] - (m + log sum exp(l - m)), at temperature 1 whatever is drawn;
+ *             written for every stepped position (at a prompt-forced position: the forced token's)
+ *   temperature == 0: the lowest index with l == m; topk and top_p are ignored
+ *   temperature  > 0: weights exp((l - m) / temperature); survivors = the topk (1..64, at most V) first tokens in the order
+ *             (logit descending, index ascending), topk == 0 = every token; top_p < 1: tau = the largest logit value among the
+ *             survivors with mass(survivors with l >= tau) >= top_p * mass(survivors), the nucleus = every survivor with
+ *             l >= tau (ties at the boundary are all kept); the pick = the first nucleus element whose running mass exceeds
+ *             u * mass(nucleus), running in the sorted order (topk >= 1) or by ascending index (topk == 0), u = the draw of
+ *             pm_dec_sample_topk keyed by (seed, cache position, row).  topk = k, temperature 1, top_p 1 picks what
+ *             pm_dec_sample_topk picks.  An entry of weight 0 is never drawn.
+ * Every reduction has one fixed order (no floating-point atomics): token and log-prob are bit-identical run to run.  Then the
+ * tail of pm_dec_next_token.  PM_EINVAL before any launch: a null pointer other than logprobs, V <= 0, ldl < V, topk outside
+ * 0..64, temperature negative / NaN / infinite, top_p outside (0, 1], d % 8 != 0.  The _ragged form takes the positional row
+ * pos[max(0, t + 1 - key_start[b])]. */
+int pm_dec_sample(const float* logits, int64_t ldl, int64_t V, int64_t topk, float temperature, float top_p, uint64_t seed,
+                  int32_t* pos_ptr, const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                  float* logprobs, const void* emb, const float* pos, float* x, int64_t d, int32_t* ticket, int64_t B,
+                  void* stream);
+int pm_dec_sample_ragged(const float* logits, int64_t ldl, int64_t V, int64_t topk, float temperature, float top_p, uint64_t seed,
+                         int32_t* pos_ptr, const int64_t* prompt, int64_t P, int64_t* tok_cur, int64_t* tokens_out, int64_t Ttot,
+                         float* logprobs, const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d,
+                         int32_t* ticket, int64_t B, void* stream);
+
 /* ConvNeXt (reference: pytorch_models/image/convnext.py), csrc/convnext.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype
  * PM_BF16 or PM_F32; gamma / beta / bias f32.  The pointwise MLP and the downsample's Conv2d(C, 2C, 2, 2) run on the GEMMs above.
  *

@@ -152,6 +152,24 @@ def ragged_sample_topk_args(logits: Tensor, k: int, seed: int, pos: Tensor, prom
             x.data_ptr(), d, ticket.data_ptr(), x.shape[0], None)
 
 
+def sample_args(logits: Tensor, topk: int, temperature: float, top_p: float, seed: int, pos: Tensor, prompt: Tensor, tok_cur: Tensor,
+                tokens: Tensor, logprobs: Tensor | None, emb: Tensor, pos_tab: Tensor, x: Tensor, ticket: Tensor) -> tuple:
+    """pm_dec_sample: the sampling tail (csrc/sample.hip); ``logprobs`` f32 like ``tokens``, or None"""
+    V, d = emb.shape
+    _unit_rows("sample_args", logits, prompt, tokens, logprobs, emb, pos_tab, x)
+    return (logits.data_ptr(), logits.stride(0), V, topk, float(temperature), float(top_p), int(seed) & (2**64 - 1), pos.data_ptr(),
+            prompt.data_ptr(), prompt.shape[1], tok_cur.data_ptr(), tokens.data_ptr(), tokens.shape[1], ptr(logprobs), emb.data_ptr(),
+            pos_tab.data_ptr(), x.data_ptr(), d, ticket.data_ptr(), x.shape[0], None)
+
+
+def ragged_sample_args(logits: Tensor, topk: int, temperature: float, top_p: float, seed: int, pos: Tensor, prompt: Tensor,
+                       tok_cur: Tensor, tokens: Tensor, logprobs: Tensor | None, emb: Tensor, pos_tab: Tensor, key_start: Tensor,
+                       x: Tensor, ticket: Tensor) -> tuple:
+    """pm_dec_sample_ragged: sample_args plus key_start; the draw stays keyed by (seed, cache position, row)"""
+    a = sample_args(logits, topk, temperature, top_p, seed, pos, prompt, tok_cur, tokens, logprobs, emb, pos_tab, x, ticket)
+    return (*a[:16], key_start.data_ptr(), *a[16:])
+
+
 def fused_args(x: Tensor, ln, w: Tensor, bias, kv: KV, out: Tensor, rows: int, heads: int, *, self_attn: bool, pos=None,
                n_keys: int) -> tuple:
     """pm_dec_attention_fused / _fused_kv32 / _fused_v2: LayerNorm + projection (+ cache append) + attention, self or cross"""

@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from .._hip import DecLayer, decode_plan as plan, lib, ops
+from .._hip.sampling import check_sampling, wants_sampling_tail
 from ..transformer import _f32
 
 
@@ -63,6 +64,31 @@ def check_ragged(what: str, lengths, *, beams: int = 1, path: str = "auto", kv32
                                   "greedy_exact: one call per distinct prompt length without lengths=")
 
 
+def check_sampling_tail(what: str, topk: int, temperature: float, top_p: float, return_logprobs: bool, *, margins: bool = False,
+                        beams: int = 1, path: str = "auto", kv32: bool = False, fp32: bool = False) -> bool:
+    """whether the sampling tail (pm_dec_sample) is asked for - temperature != 1, top_p != 1, topk == 0 or return_logprobs - and then its
+    argument checks (ValueError) and refusals, before anything touches a device: each names the form that does run"""
+    if not wants_sampling_tail(topk, temperature, top_p, return_logprobs):
+        return False
+    check_sampling(what, topk, temperature, top_p)
+    if beams != 1:
+        raise ValueError(f"{what}: temperature / top_p / topk=0 / return_logprobs draw one hypothesis per row; beam search returns "
+                         "its own scores (return_beams=True): beams=1, or these arguments at their defaults")
+    if margins:
+        raise ValueError(f"{what}: margins are an arg-max diagnostic of the default tail (topk == 1); with temperature / top_p / "
+                         "topk=0 ask for return_logprobs=True instead")
+    if path == "persistent":
+        raise NotImplementedError(f"{what}: temperature / top_p / topk=0 / return_logprobs read the full logits of the launch-per-stage "
+                                  "step; use path='launches' (or 'auto')")
+    if kv32:
+        raise NotImplementedError(f"{what}: the fp32-cache step (kv32=True / exact=True) promises the reference's arg-max ids; temperature / "
+                                  "top_p / topk=0 / return_logprobs run on the bf16-cache step: exact=False")
+    if fp32:
+        raise NotImplementedError(f"{what}: temperature / top_p / topk=0 / return_logprobs need bf16 parameters (model.to(torch.bfloat16)); "
+                                  "fp32 parameters decode through greedy_exact, arg-max only: leave these arguments at their defaults")
+    return True
+
+
 def _ragged_lengths(prompt: Tensor, lengths, longest: int | None = None) -> Tensor:
     """``lengths`` of a right-padded (B, P) prompt as int64 (B,) on the host; ValueError unless 1 <= len_b <= P (<= longest)"""
     if prompt.dim() != 2 or prompt.dtype != torch.int64 or prompt.shape[1] < 1:
@@ -92,7 +118,7 @@ class GreedyDecoder(plan.CapturedStep):
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
                  topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
                  beams: int = 1, eos: int | None = None, prefill: bool = False, prefill_chunk: int | None = None, lengths=None,
-                 pad_token_id: int = 0) -> None:
+                 pad_token_id: int = 0, *, temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False) -> None:
         """``kv32``: the reference-accuracy form of the same step - fp32 memory in, cross and self K/V kept in fp32 (nothing is
         rounded when it is cached; pm_dec_attention_fused_kv32), everything else as in the throughput path, whose projections
         are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it.
@@ -106,7 +132,13 @@ class GreedyDecoder(plan.CapturedStep):
         key_start[b] = Pm - len_b .. Pm - 1, ``P`` / ``Ttot`` / ``tokens`` / ``margins`` are in that layout (Pm + n_new wide), and
         output() shifts back.  The step keeps its one device position; the self block runs unfused (pm_dec_linear mode 1 +
         pm_dec_attention_ragged), the embedding rows take pos[max(0, t - key_start[b])].  Any ``lengths`` - all equal to P too -
-        takes this path; ``lengths=None`` builds exactly the launch list it always did."""
+        takes this path; ``lengths=None`` builds exactly the launch list it always did.
+        ``temperature`` / ``top_p`` / ``topk`` = 0 / ``return_logprobs``: the sampling tail (pm_dec_sample) in
+        place of the token choice - taken only when temperature != 1, top_p != 1, topk == 0 or return_logprobs; with the defaults
+        the launch list is the one it always was.  ``logprobs`` (B, Ttot) f32 then holds every stepped position's log-probability
+        (at temperature 1, after the rules); output_logprobs() returns the new positions in the caller's row layout."""
+        self._sampling = check_sampling_tail("greedy decode", topk, temperature, top_p, return_logprobs, margins=margins, beams=int(beams),
+                                             path=path, kv32=kv32, fp32=dec.token_embs.weight.dtype == torch.float32)
         if path not in ("auto", "launches", "persistent"):
             raise ValueError("greedy decode: path must be 'auto', 'launches' or 'persistent'")
         self.W = int(beams)
@@ -133,9 +165,9 @@ class GreedyDecoder(plan.CapturedStep):
         self.err = torch.zeros(1, dtype=torch.int32, device=self._E.device)
         if self.path == "persistent":
             self._persistent_table(dec)
-        if not 1 <= topk <= 64:
+        if not (1 <= topk <= 64 or (self._sampling and topk == 0)):
             raise ValueError("greedy decode: topk must be in 1..64")
-        self.topk = topk
+        self.topk, self.temperature, self.top_p = topk, float(temperature), float(top_p)
         self._token_tail(dec, topk, seed, rules, margins, eos)
         self._prefill_setup(dec)
 
@@ -285,6 +317,7 @@ class GreedyDecoder(plan.CapturedStep):
         self.tokens = torch.zeros(B, self.Ttot, dtype=torch.int64, device=dev)
         self.tokens[:, : self.P] = self.prompt
         self.margins = torch.zeros(B, self.Ttot, **f32) if margins else None
+        self.logprobs = torch.zeros(B, self.Ttot, **f32) if self._sampling else None  # an attribute: the plan points into it
         # d_model > 512: the final LayerNorm runs once as its own launch and the vocabulary projection without the
         # in-kernel LayerNorm, whose register budget would halve the feature tile (GPT-2 small: 101 -> ~55 us per step)
         self.split_final_norm = (d // 32 + 3) // 4 > 4
@@ -454,6 +487,13 @@ class GreedyDecoder(plan.CapturedStep):
     def _token_tail(self, dec, topk: int, seed: int, rules, margins: bool, eos) -> None:
         B, d, V, P, E, L = self.B, self.d, self.V, self.P, self._E, lib()
         xl, ln = self._final_norm(dec)
+        if self._sampling:  # full logits, the rules, then temperature / top-k / top-p / log-prob and the tail in one launch
+            self._full_logits(xl, ln, rules)
+            state = (self.logits, topk, self.temperature, self.top_p, seed, self.pos, self.prompt, self.tok_cur, self.tokens, self.logprobs,
+                     E, self._pos_tab)
+            if self._ragged:
+                return self.add(L.pm_dec_sample_ragged, *plan.ragged_sample_args(*state, self.key_start, self.x, self.ticket))
+            return self.add(L.pm_dec_sample, *plan.sample_args(*state, self.x, self.ticket))
         if topk == 1 and rules is None:
             self.linear(xl, E, None, ln=ln, mode=2)
             # token choice + the next step's embedding row + position advance: one launch
@@ -630,6 +670,13 @@ class GreedyDecoder(plan.CapturedStep):
         marg = None if self.margins is None else torch.where(live, self.margins.gather(1, idx), torch.zeros((), device=dev))
         return toks, marg
 
+    def output_logprobs(self) -> Tensor:
+        """(B, n_new) f32: the log-probability of every new token of the last run (at temperature 1, after the rules), in the caller's
+        row order - for a ragged run row b's new ids sit at state columns P .. Ttot - 1 whatever its length, as output() knows"""
+        if self.logprobs is None:
+            raise ValueError("greedy decode: this decoder was built without return_logprobs / the sampling tail")
+        return self.logprobs[:, self.P:].clone()
+
     def check(self) -> None:
         """Raise if a hand-off inside the persistent step kernel gave up (one read-back: call it where the tokens are consumed)."""
         if self.path == "persistent" and int(self.err.item()) != 0:
@@ -742,7 +789,8 @@ def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams
 @torch.no_grad()
 def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: bool = True, margins: bool = False,
                   fused: bool = True, topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto",
-                  kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None, lengths=None, pad_token_id: int = 0):
+                  kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None, lengths=None, pad_token_id: int = 0,
+                  temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False):
     """tokens (B, P + n_new) int64 [and per-position diagnostic margins].  fused=False uses the unfused
     projection + attention launches (same arithmetic, 2 more launches per layer); topk > 1 samples each token from the
     softmax over the k largest logits on the device (same seed -> same ids); path: "persistent" (all layers of a step in
@@ -754,12 +802,21 @@ def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: boo
     is prompt[b, :len_b], its n_new new ids, then P - len_b times ``pad_token_id``; margins are aligned the same way.  Row b is what
     this function returns for prompt[b:b+1, :len_b] alone.  Works with prefill, rules and top-k sampling (the draw is keyed by
     (seed, cache position, row), so a row's draws differ from those of the same row decoded alone); not with beams, path="persistent",
-    kv32 or fp32 parameters (NotImplementedError), ValueError for lengths outside 1..P or max(lengths) + n_new > max_seq_len."""
+    kv32 or fp32 parameters (NotImplementedError), ValueError for lengths outside 1..P or max(lengths) + n_new > max_seq_len.
+    ``temperature`` (finite, >= 0; 0 = arg-max), ``top_p`` in (0, 1], ``topk`` = 0 (the whole vocabulary) and ``return_logprobs`` take
+    the sampling tail (pm_dec_sample): weights exp((l - max) / temperature) over the topk first tokens (or all),
+    cut to the smallest set of highest logits whose mass reaches top_p (ties at the boundary kept), one draw keyed by (seed, cache
+    position, row).  With ``return_logprobs`` the result is (tokens, logprobs (B, n_new) f32): each new token's log-probability at
+    temperature 1 after the rules, what score() returns for it.  Works with prefill, lengths and rules; not with margins, beams
+    (ValueError), path="persistent", kv32 or fp32 parameters (NotImplementedError).  With the defaults nothing changes."""
     st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32, prefill=prefill,
-                       prefill_chunk=prefill_chunk, lengths=lengths, pad_token_id=pad_token_id)
+                       prefill_chunk=prefill_chunk, lengths=lengths, pad_token_id=pad_token_id, temperature=temperature, top_p=top_p,
+                       return_logprobs=return_logprobs)
     st.run(graph)
     st.check()
     toks, marg = st.output()
+    if return_logprobs:
+        return toks, st.output_logprobs()
     return (toks, marg) if margins else toks
 
 

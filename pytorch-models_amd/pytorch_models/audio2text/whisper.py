@@ -164,7 +164,8 @@ class WhisperDecoder(nn.Module):
     @torch.no_grad()
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0, topk: int = 1, seed: int = 0, temperature: float = 1.0,
+                 top_p: float = 1.0, return_logprobs: bool = False):
         """Batched greedy decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids.  ``rules``: a
         generate.WhisperRules (token suppression, timestamp pairing / monotonicity) applied to the logits on the device;
         ``path``: "persistent" / "launches" / "auto" (generate.GreedyDecoder).  ``beams`` > 1: beam search of that width
@@ -173,9 +174,22 @@ class WhisperDecoder(nn.Module):
         prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode; bf16 model and memory).
         ``lengths`` (B,), 1 <= len_b <= P: a ragged batch - ``prompt`` is right-padded, row b of the result is prompt[b, :len_b], its
         new ids, then P - len_b times ``pad_token_id``: what generate() returns for that clip and prompt alone (generate.greedy_decode;
-        bf16 model and memory, beams = 1, not path="persistent")."""
-        from .generate import beam_decode, check_ragged, greedy_decode, greedy_exact
+        bf16 model and memory, beams = 1, not path="persistent").
+        ``topk`` (1..64; 0 = the whole vocabulary), ``seed``, ``temperature`` (0 = arg-max), ``top_p``, ``return_logprobs`` (-> (ids,
+        logprobs (B, max_new_tokens) f32), each new token's log-probability at temperature 1 after the rules - the mean over a
+        transcript is Whisper's avg_logprob): generate.greedy_decode's sampling; bf16 model and memory, beams = 1, not
+        path="persistent"."""
+        from .generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
 
+        fp32 = self.token_embs.weight.dtype == torch.float32
+        check_sampling_tail("WhisperDecoder.generate", topk, temperature, top_p, return_logprobs,
+                            beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
+                            kv32=memory is not None and memory.dtype == torch.float32, fp32=fp32)
+        if topk != 1 and (beams != 1 or return_beams):
+            raise ValueError("beam decode: topk sampling and arg-max margins are greedy decode's")
+        if topk != 1 and fp32:
+            raise NotImplementedError("WhisperDecoder.generate: topk sampling needs bf16 parameters (model.to(torch.bfloat16)); fp32 "
+                                      "parameters decode through greedy_exact, arg-max only: topk=1")
         check_ragged("WhisperDecoder.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
                      kv32=memory is not None and memory.dtype == torch.float32, fp32=self.token_embs.weight.dtype == torch.float32)
         if prefill and self.token_embs.weight.dtype == torch.float32:
@@ -192,7 +206,8 @@ class WhisperDecoder(nn.Module):
                 raise NotImplementedError("WhisperDecoder.generate: the decoding rules run on the bf16 model's step kernels")
             return greedy_exact(self, memory, prompt, max_new_tokens)
         return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
-                             lengths=lengths, pad_token_id=pad_token_id)
+                             lengths=lengths, pad_token_id=pad_token_id, topk=topk, seed=seed, temperature=temperature, top_p=top_p,
+                             return_logprobs=return_logprobs)
 
 
 class Whisper(nn.Module):
@@ -226,16 +241,25 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",
                  exact: bool = False, beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0, topk: int = 1, seed: int = 0, temperature: float = 1.0,
+                 top_p: float = 1.0, return_logprobs: bool = False):
         """log-mel (B, n_mels, T) + prompt ids (B, P) -> greedy ids (B, P + max_new_tokens); ``beams`` > 1: beam search
         (WhisperDecoder.generate), with ``exact=True`` on the fp32-cache step (B * beams * n_heads <= 256).
         ``exact=True`` (bf16 model): the whole pipeline - encoder, cross K/V, decoder, caches - in fp32 on an fp32 copy of
         this model's (bf16-valued) weights: the ids are those of the reference's fp32 forward on the same weights, bit for
         bit (tests/test_hip_exact.py); costs ~10x the bf16 encoder and an eager fp32 step loop.  A model whose
         parameters are fp32 always decodes this way.  ``prefill``: WhisperDecoder.generate's; not with ``exact``.
-        ``lengths`` / ``pad_token_id``: WhisperDecoder.generate's ragged prompt batch; not with ``exact``, beams or fp32 parameters."""
-        from .generate import check_ragged
+        ``lengths`` / ``pad_token_id``: WhisperDecoder.generate's ragged prompt batch; not with ``exact``, beams or fp32 parameters.
+        ``topk`` / ``seed`` / ``temperature`` / ``top_p`` / ``return_logprobs``: WhisperDecoder.generate's sampling; not with ``exact``,
+        beams or fp32 parameters."""
+        from .generate import check_ragged, check_sampling_tail
 
+        check_sampling_tail("Whisper.generate", topk, temperature, top_p, return_logprobs,
+                            beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
+                            fp32=self.decoder.token_embs.weight.dtype == torch.float32)
+        if topk != 1 and exact:
+            raise NotImplementedError("Whisper.generate: exact=True promises the reference's arg-max ids; topk sampling runs on the "
+                                      "bf16-cache step: exact=False")
         check_ragged("Whisper.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
                      fp32=self.decoder.token_embs.weight.dtype == torch.float32)
         if prefill and exact:
@@ -247,7 +271,7 @@ class Whisper(nn.Module):
                 raise NotImplementedError("beam decode: bf16 weights on a HIP device only (model.to(torch.bfloat16).cuda())")
             memory = self.exact_copy().encoder(x) if exact else self.encoder(x)
             return self.decoder.generate(memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, beams=beams,
-                                         eos_token_id=eos_token_id, return_beams=return_beams, prefill=prefill)
+                                         eos_token_id=eos_token_id, return_beams=return_beams, prefill=prefill, topk=topk)
         if exact and self.decoder.token_embs.weight.dtype != torch.float32:
             # fp32 encoder on the fp32 twin of the (bf16-valued) weights; the decode step is the throughput path's own launch
             # list with fp32 K / V caches - its projections are fp32-exact as they stand (bf16 weights x activations in three
@@ -261,7 +285,8 @@ class Whisper(nn.Module):
                 return greedy_decode(self.decoder, twin.encoder(x), prompt, max_new_tokens, graph=graph, kv32=True)
             return twin.generate(x, prompt, max_new_tokens)
         return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
-                                     lengths=lengths, pad_token_id=pad_token_id)
+                                     lengths=lengths, pad_token_id=pad_token_id, topk=topk, seed=seed, temperature=temperature,
+                                     top_p=top_p, return_logprobs=return_logprobs)
 
     def exact_copy(self) -> "Whisper":
         """fp32 twin of this model (same values: bf16 -> fp32 is exact), rebuilt when a parameter changes."""

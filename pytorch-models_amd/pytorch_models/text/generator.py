@@ -18,10 +18,13 @@ class DecoderGenerator:
 
     @torch.inference_mode()
     def generate_ids(self, tokens: list[int], max_tokens: int = 100, topk: int = 1, eos_token_id: int | None = None,
-                     generator: torch.Generator | None = None, seed: int = 0, prefill: bool = False) -> list[int]:
+                     generator: torch.Generator | None = None, seed: int = 0, prefill: bool = False, *, temperature: float = 1.0,
+                     top_p: float = 1.0) -> list[int]:
         """Token-level form of generate(): prompt ids -> prompt + new ids, stopping after eos_token_id (kept, as the
         reference keeps it) or max_tokens new tokens.  ``prefill``: passed to the model's KV-cached generate() (the prompt in
-        one batched pass); a model that decodes another way refuses it."""
+        one batched pass); a model that decodes another way refuses it.  ``temperature`` (0 = arg-max) / ``top_p`` / ``topk`` = 0
+        (the whole vocabulary): the sampling tail of the KV-cached generate() (pm_dec_sample), refused likewise elsewhere."""
+        sampling = self._sampling(topk, temperature, top_p)
         p0 = next(self.model.parameters())
         device = p0.device
         tokens = list(tokens)
@@ -34,7 +37,7 @@ class DecoderGenerator:
         room = self.model.pos_embs.shape[0] - n if hasattr(self.model, "pos_embs") else max_tokens
         if topk <= 64 and hasattr(self.model, "generate") and kv_ok:
             out = self.model.generate(torch.tensor([tokens], device=device), min(max_tokens, room), topk=topk, seed=seed,
-                                      **({"prefill": True} if prefill else {}))[0].tolist()
+                                      **({"prefill": True} if prefill else {}), **sampling)[0].tolist()
             new = out[n:]
             if eos_token_id is not None and eos_token_id in new:
                 new = new[: new.index(eos_token_id) + 1]
@@ -42,6 +45,9 @@ class DecoderGenerator:
         if prefill:
             raise NotImplementedError("DecoderGenerator: prefill=True runs on the KV-cached step kernels (a bf16 pre-norm model "
                                       "with generate(): GPT-2); this model decodes token by token: prefill=False")
+        if sampling:
+            raise NotImplementedError("DecoderGenerator: temperature / top_p / topk=0 run on the KV-cached step kernels (a bf16 pre-norm "
+                                      "model with generate(): GPT-2); this model takes topk >= 1 at temperature 1, top_p 1")
         if topk == 1 and hasattr(self.model, "token_embs") and hasattr(self.model, "pos_embs"):
             from ..audio2text.generate import greedy_exact
             from ..transformer import clear_derived, derived
@@ -73,21 +79,33 @@ class DecoderGenerator:
                 break
         return tokens
 
+    @staticmethod
+    def _sampling(topk: int, temperature: float, top_p: float) -> dict:
+        """the keywords of the sampling tail for the model's generate(): empty at the defaults, which call it as always"""
+        from .._hip.sampling import check_sampling, wants_sampling_tail
+
+        if not wants_sampling_tail(topk, temperature, top_p, False):
+            return {}
+        check_sampling("DecoderGenerator", topk, temperature, top_p)
+        return dict(temperature=temperature, top_p=top_p)
+
     @torch.inference_mode()
     def generate_ids_batch(self, prompts: list[list[int]], max_tokens: int = 100, topk: int = 1, eos_token_id: int | None = None,
-                           seed: int = 0, prefill: bool = False) -> list[list[int]]:
+                           seed: int = 0, prefill: bool = False, *, temperature: float = 1.0, top_p: float = 1.0) -> list[list[int]]:
         """generate_ids() for a batch of prompts of different lengths: one ragged call of the model's KV-cached generate() per shard
         of at most 64 prompts (right-padded, ``lengths=``), the padding stripped, each row cut after its first eos_token_id (kept).
         Greedy rows are what generate_ids() returns for them; top-k draws are keyed by (seed, cache position, row) and differ from
         the row's own run.  A shard decodes min(max_tokens, room of its LONGEST prompt) new tokens per row.  A model without the
-        KV-cached step (post-norm GPT, fp32 parameters) goes through generate_ids() row by row."""
+        KV-cached step (post-norm GPT, fp32 parameters) goes through generate_ids() row by row.  ``temperature`` / ``top_p``: generate_ids()'s."""
+        sampling = self._sampling(topk, temperature, top_p)
         prompts = [list(p) for p in prompts]
         if any(len(p) == 0 for p in prompts):
             raise ValueError("DecoderGenerator: every prompt needs at least one token")
         p0 = next(self.model.parameters())
         kv_ok = p0.dtype == torch.bfloat16 and all(l.pre_norm for l in self.model.layers)
         if not (topk <= 64 and hasattr(self.model, "generate") and kv_ok):
-            return [self.generate_ids(p, max_tokens, topk, eos_token_id, seed=seed, prefill=prefill) for p in prompts]
+            return [self.generate_ids(p, max_tokens, topk, eos_token_id, seed=seed, prefill=prefill, temperature=temperature, top_p=top_p)
+                    for p in prompts]
         out = []
         for s in range(0, len(prompts), 64):
             shard = prompts[s : s + 64]
@@ -98,7 +116,7 @@ class DecoderGenerator:
             for row, p in zip(padded, shard):
                 row[: len(p)] = torch.tensor(p)
             toks = self.model.generate(padded.to(p0.device), n_new, topk=topk, seed=seed, lengths=lens, pad_token_id=0,
-                                       **({"prefill": True} if prefill else {})).tolist()
+                                       **({"prefill": True} if prefill else {}), **sampling).tolist()
             for p, row in zip(shard, toks):
                 new = row[len(p) : len(p) + n_new]
                 if eos_token_id is not None and eos_token_id in new:
@@ -106,13 +124,15 @@ class DecoderGenerator:
                 out.append(p + new)
         return out
 
-    def generate_batch(self, prompts: list[str], max_tokens: int = 100, topk: int = 1, prefill: bool = False) -> list[str]:
+    def generate_batch(self, prompts: list[str], max_tokens: int = 100, topk: int = 1, prefill: bool = False, *, temperature: float = 1.0,
+                       top_p: float = 1.0) -> list[str]:
         """generate() for a batch of prompts: one ragged batched decode (generate_ids_batch)"""
         ids = self.generate_ids_batch([self.tokenizer.encode(p) for p in prompts], max_tokens, topk,
-                                      getattr(self.tokenizer, "eos_token_id", None), prefill=prefill)
+                                      getattr(self.tokenizer, "eos_token_id", None), prefill=prefill, temperature=temperature, top_p=top_p)
         return [self.tokenizer.decode(i) for i in ids]
 
-    def generate(self, prompt: str, max_tokens: int = 100, topk: int = 1, prefill: bool = False) -> str:
+    def generate(self, prompt: str, max_tokens: int = 100, topk: int = 1, prefill: bool = False, *, temperature: float = 1.0,
+                 top_p: float = 1.0) -> str:
         ids = self.generate_ids(self.tokenizer.encode(prompt), max_tokens, topk, getattr(self.tokenizer, "eos_token_id", None),
-                                prefill=prefill)
+                                prefill=prefill, temperature=temperature, top_p=top_p)
         return self.tokenizer.decode(ids)

@@ -123,16 +123,21 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, topk: int = 1, seed: int = 0,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
-                 prefill: bool = False, lengths=None, pad_token_id: int = 0):
+                 prefill: bool = False, lengths=None, pad_token_id: int = 0, temperature: float = 1.0, top_p: float = 1.0,
+                 return_logprobs: bool = False):
         """Batched decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids; greedy (topk = 1) or
         top-k sampling on the device (softmax over the k largest logits; the same seed gives the same ids); ``beams`` > 1:
         beam search (audio2text.generate.beam_decode), with ``return_beams`` (tokens (B, beams, P + n), scores (B, beams)).
         ``prefill``: the prompt fills the caches in one batched pass instead of one step per token (generate.greedy_decode).
         ``lengths`` (B,), 1 <= len_b <= P: a ragged batch - ``prompt`` is right-padded, row b of the result is prompt[b, :len_b], its
         new ids, then P - len_b times ``pad_token_id``: what generate() returns for that row alone (greedy; top-k draws are keyed
-        by the cache position, so they differ from the row's own run).  bf16 parameters, beams = 1, not path="persistent"."""
-        from ..audio2text.generate import beam_decode, check_ragged, greedy_decode, greedy_exact
+        by the cache position, so they differ from the row's own run).  bf16 parameters, beams = 1, not path="persistent".
+        ``temperature`` (0 = arg-max), ``top_p``, ``topk`` = 0 (the whole vocabulary), ``return_logprobs`` (-> (ids, logprobs (B,
+        max_new_tokens) f32)): the sampling tail of generate.greedy_decode; bf16 parameters, beams = 1, not path="persistent"."""
+        from ..audio2text.generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
 
+        check_sampling_tail("GPT2.generate", topk, temperature, top_p, return_logprobs, beams=1 if beams == 1 and not return_beams else max(beams, 2),
+                            path=path, fp32=self.token_embs.weight.dtype == torch.float32)
         check_ragged("GPT2.generate", lengths, beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
                      fp32=self.token_embs.weight.dtype == torch.float32)
         if prefill and self.token_embs.weight.dtype == torch.float32:
@@ -148,7 +153,8 @@ class GPT2(nn.Module):
         if self.token_embs.weight.dtype == torch.float32 and topk == 1:  # fp32 parameters: fp32 end to end
             return greedy_exact(self, None, prompt, max_new_tokens)
         return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path, prefill=prefill,
-                             lengths=lengths, pad_token_id=pad_token_id)
+                             lengths=lengths, pad_token_id=pad_token_id, temperature=temperature, top_p=top_p,
+                             return_logprobs=return_logprobs)
 
     @staticmethod
     def from_hf(model_tag: str, *, pretrained=False, **kwargs) -> "GPT2":

@@ -185,6 +185,8 @@ CASES = {
     "whisper_kv32": _greedy(kv32=True),
     "whisper_kv32_no_chain": _greedy(kv32=True, env={"PM_DEC_CHAIN": "0"}),  # pm_dec_attention_fused_kv32
     "whisper_topk4": _greedy(topk=4),
+    "whisper_sample": _greedy(topk=0, temperature=0.7, top_p=0.9, return_logprobs=True, rules=True),  # pm_dec_sample: the log-prob buffer
+    "whisper_logprobs": _greedy(return_logprobs=True),  # the arg-max of the defaults through the sampling tail
     "whisper_rules": _greedy(rules=True),
     "whisper_margins": _greedy(margins=True),
     "whisper_mlp256": _greedy(model=dict(hid=256)),  # no K-split anywhere
