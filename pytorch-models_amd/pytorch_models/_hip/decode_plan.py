@@ -205,6 +205,9 @@ class CapturedStep:
     (which ends in start()) and the run loop (which starts with begin())."""
 
     def __init__(self, rows: int, device, k_split: int, ksplit_min_k: int) -> None:
+        from . import ops  # (ops imports this module)
+
+        ops.no_capture(type(self).__name__, "builds caches, uploads its tables and captures a graph of its own")
         self.launches, self._keep, self._ks_cnts, self._graph = [], [], [], None
         self._n_rows, self._device, self._k_split, self._ksplit_min_k = rows, device, k_split, ksplit_min_k
         self._model, self._model_sig = None, None

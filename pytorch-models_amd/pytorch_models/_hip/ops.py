@@ -83,6 +83,21 @@ def _need(cond: bool, msg: str) -> None:
         raise ValueError(msg)
 
 
+def capturing() -> bool:
+    """The current stream is being captured into a HIP graph.  False wherever no HIP context exists (a process that has not
+    touched the GPU cannot be capturing), so the host-only helpers below stay usable without one."""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+def no_capture(who: str, why: str) -> None:
+    """The capture guard: a wrapper or helper that reads device memory on the host, uploads host values or
+    synchronises calls this FIRST, in front of any device access.  Under stream capture such a call would either die inside the
+    HIP runtime or bake the values of capture time into the graph; it raises instead, naming itself."""
+    if capturing():
+        raise RuntimeError(f"{who}: {why}, which a stream capture (torch.cuda.graph, GraphedForward) cannot record - "
+                           "call it outside the capture and pass device tensors in")
+
+
 def _cuda(*ts: Tensor) -> None:
     check_devices(*ts)
 
@@ -567,6 +582,7 @@ def stft_tables(window: Tensor, n_fft: int) -> tuple[Tensor, Tensor, bool]:
     says which."""
     nbins = n_fft // 2 + 1
     nblk = (nbins + 31) // 32
+    no_capture("stft_tables", "builds its tables on the host from the window and uploads them")
     w = window.detach().double().cpu()
     # symmetric up to the rounding of the window's own construction (torch.hann_window: 3e-7 between w[k] and w[N - k] in fp32);
     # the folded form then uses the mean of the two - a relative change of 1.5e-7 per term, two orders below the parity tolerance
@@ -597,6 +613,7 @@ def stft_tables(window: Tensor, n_fft: int) -> tuple[Tensor, Tensor, bool]:
 
 def mel_csr(filters: Tensor) -> tuple[Tensor, Tensor, Tensor]:
     """CSR form (int32 row pointers, int32 columns, f32 values) of a dense (n_mels, nbins) filterbank."""
+    no_capture("mel_csr", "reads the filterbank on the host and uploads its CSR form")
     f = filters.detach().float().cpu()
     nz = f != 0
     ptr = torch.zeros(f.shape[0] + 1, dtype=torch.int32)
@@ -725,6 +742,7 @@ def dec_linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, ln: tuple | 
 def dec_linear_ksplit(x: Tensor, w: Tensor, bias: Tensor | None = None, *, k_split: int, act: str = "none",
                       resid: Tensor | None = None) -> Tensor:
     """dec_linear without LayerNorm, K split over k_split workgroups per 16-feature tile (pm_dec_linear_ksplit)."""
+    no_capture("dec_linear_ksplit", "reads its ticket counters back after the launch")
     _cuda(x, w, bias, resid)
     M, N, K = _dec_rows("dec_linear_ksplit", x, w, bias, resid, None)
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
@@ -894,7 +912,8 @@ def dec_embed_ragged(tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, pos: Tensor,
     _key_start(key_start, B, "dec_embed_ragged")
     _need(emb.dtype == torch.bfloat16 and pos_tab.dtype == torch.float32 and pos.dtype == torch.int32 and tok_cur.dtype == torch.int64,
           "dec_embed_ragged: bf16 table, f32 positions, int32 position, int64 tokens")
-    _need(0 <= int(pos) < pos_tab.shape[0], "dec_embed_ragged: position outside the positional table")
+    # (a validation that reads *pos back: not under capture, where the position is whatever the replay finds there)
+    _need(capturing() or 0 <= int(pos) < pos_tab.shape[0], "dec_embed_ragged: position outside the positional table")
     x = torch.empty(B, emb.shape[1], dtype=torch.float32, device=emb.device)
     plan.call(lib().pm_dec_embed_ragged, plan.ragged_embed_args(tok_cur, emb, pos_tab, pos, key_start, x), _stream())
     return x
@@ -907,7 +926,9 @@ def _tail_state(what: str, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens:
           and tokens.shape[0] == B and tokens.shape[1] >= prompt.shape[1] and tok_cur.dtype == torch.int64 and tok_cur.shape == (B,) and tok_cur.is_contiguous(),
           f"{what}: contiguous int64 prompt (B, P), tokens (B, Ttot >= P), tok_cur (B,)")
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
-          and pos_tab.shape[1] == emb.shape[1] and 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: bf16 table, f32 positions covering position + 1")
+          and pos_tab.shape[1] == emb.shape[1], f"{what}: bf16 table, f32 positions")
+    # (a validation that reads *pos back: not under capture, where the position is whatever the replay finds there)
+    _need(capturing() or 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: the positional table must cover position + 1")
 
 
 def dec_next_token(ws_val: Tensor, ws_idx: Tensor, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens: Tensor, emb: Tensor,
@@ -961,6 +982,8 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
                       max_initial_timestamp: int = -1, suppress=(), blank=()) -> Tensor:
     """pm_dec_whisper_rules as a standalone op (the generator puts it into its launch list): filters logits (B, V) f32 IN PLACE for
     the token at index pos + 1 of tokens (B, Ttot) int64; returns logits."""
+    if len(suppress) or len(blank):
+        no_capture("dec_whisper_rules", "uploads the suppress / blank id lists")
     _cuda(logits, tokens, pos)
     _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and _apart(logits),
           "dec_whisper_rules: logits f32 (B, V) rows that do not overlap")
@@ -1038,6 +1061,7 @@ def dec_beam_select(cand_score: Tensor, cand_tok: Tensor, scores: Tensor, finish
 def dec_beam_reorder(caches: list[Tensor], parents: Tensor, pos: Tensor) -> None:
     """pm_dec_beam_reorder as a standalone op: every cache (B * W, H, Tmax, 64) (all bf16 or all f32, one geometry) is re-gathered
     IN PLACE, rows 0 .. pos - 1 of row (b, j) from row (b, parents[b, j])."""
+    no_capture("dec_beam_reorder", "reads parents and pos on the host, uploads its pointer table and synchronises")
     _cuda(parents, pos, *caches)
     B, W = parents.shape
     _need(parents.dtype == torch.int32 and parents.is_contiguous(), "dec_beam_reorder: parents int32 (B, W)")
@@ -1699,6 +1723,7 @@ def align_counts(v, n: int, lo: int, hi: int, name: str, device) -> Tensor:
     if isinstance(v, Tensor) and v.is_cuda:
         _need(v.dtype == torch.int32 and v.shape == (n,) and v.is_contiguous(), f"{name} must be a contiguous int32 ({n},) tensor")
         return v
+    no_capture(name.split(":")[0], f"uploads {name.split(':')[-1].strip()} from the host")
     vals = [int(v)] * n if isinstance(v, int) else [int(x) for x in (v.tolist() if isinstance(v, Tensor) else v)]
     _need(len(vals) == n and all(lo <= x <= hi for x in vals), f"{name} must hold {n} values in [{lo}, {hi}], got {vals}")
     return torch.tensor(vals, dtype=torch.int32).to(device)
@@ -1799,6 +1824,7 @@ class SeqLens:
 def seq_lens(lengths, L: int, device, lo: int = 0) -> SeqLens:
     """lengths: B host ints, or a 1-D integer tensor (read back once), each in [lo, L] -> SeqLens with cu_seqlens on ``device``
     (one upload, in front of every launch).  Validated on the host: the kernels trust cu_seqlens."""
+    no_capture("seq_lens", "reads the lengths on the host and uploads cu_seqlens")
     if isinstance(lengths, Tensor):
         _need(lengths.dim() == 1 and not lengths.dtype.is_floating_point and lengths.dtype != torch.bool,
               f"lengths must be a 1-D integer tensor, got {tuple(lengths.shape)} {lengths.dtype}")
@@ -2040,6 +2066,8 @@ def ctc_greedy(best: Tensor, seq: SeqLens, best_logp: Tensor | None = None, blan
 
 
 def _ctc_rec(who: str, logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, blank: int):
+    if not (isinstance(target_lengths, Tensor) and target_lengths.is_cuda):
+        no_capture(who, "uploads target_lengths from the host")
     _need(logp.dim() == 2 and logp.dtype == torch.float32 and logp.stride(1) == 1, f"{who}: logp must be f32 (T_total, V) with a unit last stride")
     _need(isinstance(targets, Tensor) and targets.dim() == 2 and targets.dtype == torch.int32 and (targets.shape[1] == 0 or targets.stride(1) == 1),
           f"{who}: targets must be int32 (B, Umax) with a unit last stride")

@@ -54,7 +54,17 @@ class Wav2Vec2CTC(nn.Module):
             return self.encoder._packed_rows(x, [n] * x.shape[0])
         h = self.encoder(x)
         B, T, d = h.shape
-        return h.reshape(B * T, d), ops.seq_lens([T] * B, T, h.device)
+        return h.reshape(B * T, d), self._full_seq(B, T, h.device)
+
+    def _full_seq(self, B: int, T: int, device):
+        """The extents of a batch whose clips all run to the last frame: built (one upload) at the first call of a geometry and
+        KEPT per (B, T, device) - a captured forward holds the pointer of ``cu``, so a call at another geometry in between must
+        not replace it, and a replay must not upload.  clear_derived drops the table."""
+        cache = self.__dict__.setdefault("_pm_tables", {})
+        key = (B, T, str(device))
+        if key not in cache:
+            cache[key] = ops.seq_lens([T] * B, T, device)
+        return cache[key]
 
     def _head(self, x: Tensor, lengths):
         """(logp f32 (sum frames, V), best int32, best_logp f32, SeqLens)"""
@@ -99,6 +109,7 @@ class Wav2Vec2CTC(nn.Module):
     def _targets(self, targets, target_lengths, B: int, device):
         """Host validation in front of every launch -> (targets int32 (B, max(target_lengths)) on ``device``, target_lengths
         list): columns no clip uses are trimmed before the launch (align pads its outputs back to the width passed in)."""
+        ops.no_capture("Wav2Vec2CTC", "reads targets and target_lengths on the host")
         t = torch.as_tensor(targets)
         if t.dim() != 2 or t.dtype.is_floating_point or t.dtype == torch.bool:
             raise ValueError(f"Wav2Vec2CTC: targets must be an integer (B, U) tensor, got {tuple(t.shape)} {t.dtype}")

@@ -175,6 +175,7 @@ def align(dec, tokens: Tensor, memory: Tensor, *, lengths=None, frames=None, hea
           return_matrix: bool = False):
     """WhisperDecoder.align (documented there)."""
     who = "WhisperDecoder.align"
+    ops.no_capture(who, "uploads its counts and head tables and back-traces the path on the host")
     sa = dec.layers[0].sa
     hs, lens, frs = check_args(who, tokens, memory, len(dec.layers), sa.n_heads, heads, lengths, frames, skip_first, skip_last)
     w = dec.token_embs.weight

@@ -33,7 +33,7 @@ from torch import Tensor, nn
 
 from .. import _cpu
 from .._hip import ops
-from ..transformer import MHA, DecoderLayer, EncoderLayer, LayerNorm, _f32, _wb, derived, require_bf16_params
+from ..transformer import MHA, DecoderLayer, EncoderLayer, LayerNorm, _f32, _sig, _wb, derived, require_bf16_params
 from .vit import _no_download
 
 
@@ -158,9 +158,11 @@ class ResNet(nn.Module):
 # ------------------------------------------------------------------------------------------------ transformer layers
 def _embed_table(mha: MHA, names: str, emb: Tensor, n_emb: int) -> Tensor:
     """f32 (rows, len(names) * inner): the packed projection of the position rows ``emb`` plus the biases; the first ``n_emb``
-    projections see the embedding (W emb + b), the others only their bias - the reference adds it to q and k, never to v."""
+    projections see the embedding (W emb + b), the others only their bias - the reference adds it to q and k, never to v.
+    One table per embedding tensor is KEPT: the position rows differ with the feature map's (h, w), and a captured forward
+    holds the pointer of the table it was captured with, so a call at another image size must add a table, never replace one
+    (class 5).  The derived() entry is the dict of the tables of one state of the projections."""
     mods = [getattr(mha, f"{n}_proj") for n in names]
-    params = [m.weight for m in mods] + [m.bias for m in mods] + [emb]
 
     def build():
         e = emb.detach().float()
@@ -170,7 +172,15 @@ def _embed_table(mha: MHA, names: str, emb: Tensor, n_emb: int) -> Tensor:
             cols.append(e @ m.weight.detach().float().t() + b if i < n_emb else b.expand(e.shape[0], -1))
         return torch.cat(cols, 1).contiguous()
 
-    return derived(mha, f"embed_{names}_{n_emb}", params, build)
+    tables = derived(mha, f"embed_{names}_{n_emb}", [m.weight for m in mods] + [m.bias for m in mods], dict)
+    sig = _sig((emb,))
+    hit = tables.get(id(emb))
+    if hit is None or hit[0] is not emb or hit[1] != sig:  # (the kept tensor cannot lend its id to another)
+        with torch.no_grad():
+            hit = tables[id(emb)] = (emb, sig, build())
+        if not ops.capturing():
+            torch.cuda.current_stream().synchronize()  # as derived(): built on this stream, used from any
+    return hit[2]
 
 
 def _attn_out(mha: MHA, o: Tensor, resid: Tensor) -> Tensor:
@@ -455,6 +465,7 @@ class DETRPipeline(nn.Module):
 
     @torch.no_grad()
     def forward(self, images: list[Tensor], th: float | None = None):
+        ops.no_capture("DETRPipeline", "builds Python lists from the detections on the host")
         height = max(img.shape[-2] for img in images)
         width = max(img.shape[-1] for img in images)
         batch = torch.stack([F.pad(img, (0, width - img.shape[-1], 0, height - img.shape[-2])) for img in images], dim=0)

@@ -59,6 +59,7 @@ def score_targets(tokens: Tensor, lengths, who: str) -> Tensor:
     tgt = tokens[:, 1:]
     if lengths is None:
         return tgt.contiguous()
+    ops.no_capture(who, "reads lengths on the host")
     lens = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
     if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > L:
         raise ValueError(f"{who}: lengths must hold {B} values in [1, {L}], got {lens.tolist()}")

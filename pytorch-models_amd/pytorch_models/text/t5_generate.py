@@ -230,6 +230,7 @@ def _signature(model) -> tuple:
 @torch.no_grad()
 def generate(model, input_ids: Tensor, *, lengths=None, max_new_tokens: int = 100, pad_id: int = 0, eos_id: int = 1,
              decoder_prompt: Tensor | None = None, graph: bool = True, return_logits: bool = False, packed: bool = False):
+    ops.no_capture("T5Model.generate", "reads ids and lengths on the host and captures a graph of its own")
     require_bf16_params(model, "T5Model.generate")
     if not isinstance(input_ids, Tensor) or input_ids.dtype != torch.int64 or input_ids.dim() != 2:
         raise ValueError("T5Model.generate: input_ids must be int64 (B, S), right-padded")

@@ -81,3 +81,86 @@ def test_mixer_token_mix_plan_is_a_host_side_query():
     assert list(rep) == [4, 55296 + 100352, 55296, 13, 24, 12, 7, 0, -1, -1]
     assert L.pm_mixer_token_mix_plan(1, 32, 64, p) == 0
     assert list(rep)[:8] == [2, 33792 + 64 * 40 * 2, 33792, 1, 2, 1, 1, 1]  # NB 2 (C % 128), region_a = 8 waves x 32 x 33 x 4 B of scratch
+
+
+# ---- the types, not only the names: every argtypes list and restype against the header's prototypes
+_C_TYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
+
+
+def _strip(src: str) -> str:
+    """the header without comments and preprocessor lines"""
+    import re
+
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    return "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
+
+
+def _ctype(decl: str, name: bool):
+    """the ctypes type of one C declarator: a pointer is c_void_p (``const char*``: c_char_p), a scalar by its type name"""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return ctypes.c_char_p if words[:2] == ["const", "char"] else ctypes.c_void_p
+    words = [w for w in words if w != "const"]
+    assert len(words) == (2 if name else 1), decl
+    return _C_TYPES[words[0]]
+
+
+def _prototypes(path: str) -> dict:
+    import re
+
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s\*]+)(pm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _strip(open(path).read())):
+        params = params.strip()
+        args = [] if params in ("", "void") else [_ctype(p.strip(), True) for p in params.split(",")]
+        assert name not in out, f"{name} declared twice"
+        out[name] = (args, _ctype(ret.strip(), False))
+    return out
+
+
+def _mismatches(table: dict, protos: dict) -> list:
+    bad = [f"{n}: in the table, not in the header" for n in table if n not in protos]
+    for n, (args, ret) in protos.items():
+        if n not in table:
+            bad.append(f"{n}: declared, not in the table")
+            continue
+        targs, tret = table[n]
+        if len(targs) != len(args):
+            bad.append(f"{n}: {len(targs)} argtypes for {len(args)} parameters")
+        bad += [f"{n}: argument {i} is {t.__name__} in the table, {a.__name__} in the header" for i, (t, a) in enumerate(zip(targs, args)) if t is not a]
+        if tret is not ret:
+            bad.append(f"{n}: restype {tret.__name__} in the table, {ret.__name__} in the header")
+    return bad
+
+
+def test_signature_table_matches_the_header_prototypes_type_by_type():
+    """sorted(SIGNATURES) == the declared names says nothing about the 119 hand-written argtypes lists: a c_int where the header
+    takes an int64_t passes the upper half of a stride as the next argument's garbage on no platform ctypes checks."""
+    protos = _prototypes(_hip.HEADER_PATH)
+    assert len(protos) == len(_hip.header_functions()), sorted(set(_hip.header_functions()) ^ set(protos))
+    bad = _mismatches(_hip.SIGNATURES, protos)
+    assert not bad, "\n".join(bad)
+    args, ret = _hip.SIGNATURES["pm_linear_bf16"]  # the comparison itself: one stride narrowed to an int must be reported
+    assert args[1] is ctypes.c_int64 and _mismatches({**_hip.SIGNATURES, "pm_linear_bf16": ([args[0], ctypes.c_int] + args[2:], ret)}, protos)
+
+
+def test_experiment_signatures_and_dec_layer_match_their_header():
+    import re
+
+    path = os.path.join(os.path.dirname(_hip.HEADER_PATH), "pm_mi355x_experiments.h")
+    bad = _mismatches(_hip.EXPERIMENT_SIGNATURES, _prototypes(path))
+    assert not bad, "\n".join(bad)
+    body = re.search(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*pm_dec_layer_t\s*;", _strip(open(path).read()), flags=re.S)
+    assert body, "pm_dec_layer_t not found"
+    fields = []
+    for decl in body.group(1).split(";"):
+        if not decl.strip():
+            continue
+        head, *more = [d.strip() for d in decl.split(",")]  # "const void *a, *b" or "float x, y"
+        base = head.replace("*", " * ").split()
+        star, base_name = "*" in base, base[-1]
+        ctype = _ctype(head, True)
+        fields.append((base_name, ctype))
+        for m in more:
+            fields.append((m.replace("*", "").strip(), ctypes.c_void_p if "*" in m else (ctype if not star else _C_TYPES[[w for w in base if w not in ("const", "*")][0]])))
+    assert fields == list(_hip.DecLayer._fields_), (fields, _hip.DecLayer._fields_)
