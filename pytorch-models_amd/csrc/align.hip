@@ -123,9 +123,12 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(const bf16* __restric
                                                            float* __restrict__ Mo, int64_t ldm, int64_t mbs, int L, int S, int nh,
                                                            int H, float inv_heads, int first) {
   __shared__ float P[AL_MAXL * MT_PS];
+  __shared__ int bad_tile;  // a column of this tile holds a NaN probability (a NaN in q, k or lse): see the store below
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int b = blockIdx.y, f0 = blockIdx.x * MT_W;
+  if (tid == 0) bad_tile = 0;  // (the first barrier of the head loop is in front of every other write and every read of it: the
+                               // launcher refuses nh < 1, so the loop runs at least once)
   const int len = al_clamp(lengths[b], 1, L), F = al_clamp(frames[b], 1, S);
   const int nout = al_clamp((F < f0 + MT_W ? F : f0 + MT_W) - f0, 0, MT_W);  // frames of this tile below F
   const int wcols = (S < f0 + MT_W ? S : f0 + MT_W) - f0;                     // frames of this tile below S
@@ -184,6 +187,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(const bf16* __restric
           vmin = fminf(vmin, __shfl_xor(vmin, mask, 64));
         }
         const bool flat = vmax == vmin;  // all rows equal: the std is exactly 0 whatever the rounding of the mean
+        if (part == 0 && sum != sum) bad_tile = 1;  // (every writer writes 1)
         const float mean = sum / (float)len;
         // exact power-of-two scale 2^(127 - e) of the deviations, e the biased exponent of the mean (p <= 1, so e <= 127)
         int e = (__float_as_int(mean) >> 23) & 255;
@@ -237,13 +241,15 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(const bf16* __restric
       }
       __syncthreads();
     }
-    // the tile's result through LDS, so that the store below runs along the frames
+    // the tile's result through LDS, so that the store below runs along the frames.  The normalisation (sd > 0 is false for a NaN
+    // deviation) and the median's min / max exchanges both drop a NaN; a tile that met one reports NaN instead of looking healthy
+    const bool bad = bad_tile != 0;  // (behind the head loop's last barrier)
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
       const int t = tid + rr * 256;
       if (t < len) {
 #pragma unroll
-        for (int o = 0; o < MT_W; ++o) P[t * MT_PS + o] = acc[rr][o] * inv_heads;
+        for (int o = 0; o < MT_W; ++o) P[t * MT_PS + o] = bad ? __builtin_nanf("") : acc[rr][o] * inv_heads;
       }
     }
     __syncthreads();

@@ -146,7 +146,10 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const T* __restrict__
     mx = wave_max(mx);
     float sum = 0.f;
     for (int k = lane; k < Lk; k += 64) {
-      const float p = mx == -INFINITY ? 0.f : expf(sc[qq * GMAXK + k] - mx);  // dead row: no -inf - -inf
+      // dead row: no -inf - -inf.  Only a score that IS -inf is dead: a row of NaN scores (fmaxf skips them, so mx is -inf too)
+      // keeps its NaN - p, the sum and the output are NaN - instead of returning the zeros of a masked row
+      const float s = sc[qq * GMAXK + k];
+      const float p = (mx == -INFINITY && s == -INFINITY) ? 0.f : expf(s - mx);
       sc[qq * GMAXK + k] = p;
       sum += p;
     }

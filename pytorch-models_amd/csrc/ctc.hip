@@ -204,11 +204,12 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const int* __restrict__
 template <bool VIT>
 __device__ __forceinline__ float ct_step(float a, float b, float c, unsigned& code) {
   if constexpr (VIT) {
-    if (a >= b && a >= c) {
+    // NaN ranks above everything (x != x), as in torch.max: a NaN emission reaches the score instead of losing every comparison
+    if ((a >= b || a != a) && (a >= c || a != a)) {
       code = 0u;
       return a;
     }
-    if (b >= c) {
+    if (b >= c || b != b) {
       code = 1u;
       return b;
     }

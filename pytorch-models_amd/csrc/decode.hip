@@ -1417,6 +1417,7 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
   }
   float bv = -INFINITY, second = -INFINITY;
   int bi = 0x7fffffff;
+  bool bad = false;  // a NaN among the row's tile maxima: no comparison sees it, the margin reports it
   // four (value, index) pairs per thread requested together, branch-free (clamped index, the repeats dropped below): one
   // request per loop trip made every trip a dependent memory round trip (811 tiles = 4 trips per thread at Whisper's vocabulary)
   for (int i0 = tid; i0 < nwg; i0 += 4 * 256) {
@@ -1435,6 +1436,7 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
       const int ix = i0 + 256 * j < nwg ? x4[j] : 0x7fffffff;
       if (v > bv || (v == bv && ix < bi)) { second = fmaxf(second, bv); bv = v; bi = ix; }
       else second = fmaxf(second, v);
+      bad |= v != v;
     }
   }
   // (winner, runner-up) over the wave: partners 1, 2 lanes away by quad permutes, 4 by the half row's mirror (the quads are
@@ -1464,12 +1466,16 @@ __global__ __launch_bounds__(256) void dec_argmax_reduce_kernel(const float* __r
     comb(__uint_as_float(rv[sel]), (int)ri[sel], __uint_as_float(r2[sel]));
   }
   if (lane == 0) { sv[wave] = bv; si[wave] = bi; s2[wave] = second; }
-  __syncthreads();
+  const bool any_bad = __syncthreads_or(bad);
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) {
       if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { second = fmaxf(fmaxf(second, s2[w]), bv); bv = sv[w]; bi = si[w]; }
       else second = fmaxf(fmaxf(second, s2[w]), sv[w]);
     }
+    // a row without a maximum - every tile at -inf (its winners carry no index) or NaN - takes index 0: torch.argmax's answer
+    // for the row of -inf, a valid id for the row of NaN.  Its margin is -inf - -inf = NaN; so is the margin of a row with a NaN.
+    if (bi == 0x7fffffff) bi = 0;
+    if (any_bad) second = __builtin_nanf("");
     const int64_t next = (t1 < P) ? forced : (int64_t)bi;
     tok_cur[b] = next;
     if (t + 1 < Ttot) tokens_out[(int64_t)b * Ttot + t + 1] = next;
@@ -1659,7 +1665,9 @@ __global__ __launch_bounds__(256) void dec_sample_topk_kernel(const float* __res
       for (int r = k - 1; r >= 0; --r)
         if (u < cum[r]) pick = r;
     }
-    const int64_t next = (t + 1 < P) ? prompt[(int64_t)b * P + t + 1] : (int64_t)topi[pick];
+    int ti = topi[pick];  // a round that found nothing (fewer than k comparable logits, or a row of NaN) carries no index
+    if (ti == 0x7fffffff) ti = topi[0] == 0x7fffffff ? 0 : topi[0];
+    const int64_t next = (t + 1 < P) ? prompt[(int64_t)b * P + t + 1] : (int64_t)ti;
     tok_cur[b] = next;
     if (t + 1 < Ttot) tokens_out[(int64_t)b * Ttot + t + 1] = next;
     snext = next;

@@ -119,7 +119,18 @@ __global__ __launch_bounds__(TW_THREADS) void dec_beam_topw_kernel(const float* 
     }
     if (tid == 0) {
       cs[k] = bv > -INFINITY ? s + (bv - lse) : -INFINITY;
-      ct[k] = bi;
+      // fewer than W comparable logits (NaN compares with nothing): the lowest id no earlier round of this row took, at -inf -
+      // the row's W candidates stay distinct (some id in 0 .. k is free: k earlier rounds, k + 1 <= W <= V ids)
+      int tok = bi;
+      if (bi == NONE) {
+        tok = 0;
+        for (int c = k; c >= 0; --c) {
+          bool used = false;
+          for (int j = 0; j < k; ++j) used = used || ct[j] == c;
+          if (!used) tok = c;
+        }
+      }
+      ct[k] = tok;
     }
     __syncthreads();
   }
@@ -163,7 +174,11 @@ __global__ __launch_bounds__(256) void dec_beam_select_kernel(const float* __res
         for (int o = 0; o < n; ++o) {  // o / W = parent, ascending with o: equal scores of another row -> the lower o is first
           const float os = c_s[o];
           const int ot = c_t[o];
-          const bool before = ot >= 0 && (os > ms || (os == ms && (o / W < tid / W || (o / W == tid / W && ot < mt))));
+          // NaN scores come first and tie with each other (torch.topk's order): the order stays total, so no two candidates
+          // share a rank, and a NaN hypothesis stays visible in `scores` instead of racing the best finite one for slot 0
+          const bool on = os != os, mn = ms != ms;
+          const bool gt = mn ? false : (on || os > ms), eq = mn ? on : os == ms;
+          const bool before = ot >= 0 && (gt || (eq && (o / W < tid / W || (o / W == tid / W && ot < mt))));
           rank += before ? 1 : 0;
         }
       if (rank < W) {

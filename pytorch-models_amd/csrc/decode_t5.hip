@@ -355,6 +355,7 @@ __global__ __launch_bounds__(T5_THREADS) void t5_next_token_kernel(
   if (tid == 0) {
     for (int w = 1; w < 4; ++w)
       if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+    if (bi == 0x7fffffff) bi = 0;  // a row without a maximum (every tile at -inf, or NaN): index 0, as torch.argmax on -inf
     int64_t next;
     if (t1 < P) {
       next = prompt[(int64_t)b * P + t1];

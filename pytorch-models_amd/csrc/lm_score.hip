@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void lm_score_merge_kernel(const float* __rest
   const int64_t t = targets[m];
   logprob[m] = (t >= 0 && t < V) ? a.tg - l : 0.f;
   if (lse) lse[m] = l;
-  if (argmax) argmax[m] = a.bi;
+  if (argmax) argmax[m] = (unsigned)a.bi < (unsigned)V ? a.bi : 0;  // a row without a maximum (NaN): any valid index
 }
 
 }  // namespace

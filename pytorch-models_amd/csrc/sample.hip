@@ -115,10 +115,13 @@ __global__ __launch_bounds__(SP_THREADS) void dec_sample_kernel(const float* __r
   // rescale.  -inf entries add nothing; a lane that has seen only -inf keeps (max -inf, sum 0).
   float mt = -INFINITY, st = 0.f;
   int bi = 0x7fffffff;
+  bool bad = false;  // a NaN logit: no comparison below sees it, so the sum is made to carry it
   for (int i0 = lo + lane; i0 < hi; i0 += 4 * 64) {
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = i0 + 64 * j < hi ? row[i0 + 64 * j] : -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bad |= v[j] != v[j];
     float mn = mt;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -133,6 +136,9 @@ __global__ __launch_bounds__(SP_THREADS) void dec_sample_kernel(const float* __r
       mt = mn;
     }
   }
+  // NaN * exp(.) stays NaN through every merge that forms a sum: lse, and with it the log-prob, is NaN.  A merge of two parts at
+  // -inf forms none, so a row of NaN and -inf only ends with m = -inf and reports the log-prob -inf, as a row of -inf does.
+  if (bad) st = __builtin_nanf("");
   auto merge = [&](float om, float os, int oi) {  // (max, sum, index) of two disjoint parts; the part with the lower indices is `this`
     const float mn = fmaxf(mt, om);
     if (om > mt || (om == mt && oi < bi)) bi = oi;
@@ -154,7 +160,8 @@ __global__ __launch_bounds__(SP_THREADS) void dec_sample_kernel(const float* __r
   for (int w = 1; w < SP_WAVES; ++w) merge(sh.f[w][0], sh.f[w][1], sh.i[w]);
   const float m = mt;
   const float lse = m + logf(st);  // m == -inf (a row of -inf only): -inf, and the log-prob below is reported as -inf
-  const int amax = bi;             // every thread holds (m, lse, amax), from the same operations in the same order
+  const int amax = bi == 0x7fffffff ? 0 : bi;  // a row of NaN has no maximum: a valid id.  Every thread holds (m, lse, amax), from
+                                               // the same operations in the same order
 
   int pick = amax;
   if (T > 0.f && k >= 1) {

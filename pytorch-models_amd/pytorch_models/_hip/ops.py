@@ -765,7 +765,9 @@ def dec_argmax(x: Tensor, w: Tensor, ln: tuple) -> tuple[Tensor, Tensor]:
     plan.call(lib().pm_dec_linear, plan.linear_args(x, w, None, M, ln=ln, mode=2, argmax_ws=(wv, wi)), _stream(), "pm_dec_linear(argmax)")
     best = wv.max(1)
     cand = torch.where(wv == best.values[:, None], wi, torch.full_like(wi, 2**31 - 1))
-    return cand.min(1).values.long(), best.values
+    idx = cand.min(1).values.long()
+    # a row without a maximum (LN(x) not finite: every tile reports -inf and no index): index 0, as pm_dec_next_token writes
+    return torch.where(idx == 2**31 - 1, torch.zeros_like(idx), idx), best.values
 
 
 DEC_LINEAR_PLAN_FIELDS = ("kernel", "MT", "FT", "NSTEP", "LN", "waves", "gx", "gy", "gz", "tiles")

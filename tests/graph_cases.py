@@ -166,9 +166,12 @@ def row_sets(r: WC.Row, dev) -> tuple[dict, dict]:
     drawn values (the CSR form of a random filterbank) is structure, not data: set b takes set a's.  Every floating-point
     operand of the same shape must differ between the sets, or the case proves nothing."""
     a, b = r.build(dev), r.build(dev, SEED_B)
+    # (a structure is taken whole: the CSR triple's row pointers always have one shape, and set b's pointers over set a's shorter
+    # column and value arrays sent the kernel past their end - results that depended on what lay behind them)
+    whole = {path[0] for path, t in WC.operands(a) if WC.get(b, path).shape != t.shape or WC.get(b, path).dtype != t.dtype}
     for path, t in WC.operands(a):
         u = WC.get(b, path)
-        if u.shape != t.shape or u.dtype != t.dtype:
+        if path[0] in whole:
             b = WC.replaced(b, path, t.clone())
         elif t.is_floating_point() and t.numel() and WC.same_bits(t, u) and (r.id, path[0]) not in SHARED and \
                 not (path[0] in r.inplace and not bool(t.any())):  # (a zeroed output buffer is not data)
