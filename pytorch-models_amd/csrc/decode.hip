@@ -1868,6 +1868,7 @@ extern "C" int pm_dec_linear(const float* x, int64_t ldx, const float* gamma, co
   if (!x || !w || M <= 0 || N <= 0 || K <= 0) return PM_EINVAL;
   if (M > 64 || K % 32) return PM_EUNSUPPORTED;
   if (ldx < K || ldw < K || ldx % 4 || ldw % 8) return PM_EALIGN;
+  if (ldx > 0x7fffffff || ldr > 0x7fffffff || ldo > 0x7fffffff) return PM_EINVAL;  // the kernels take these strides as int
   if (((uintptr_t)x | (uintptr_t)w) & 15) return PM_EALIGN;
   if ((gamma == nullptr) != (beta == nullptr)) return PM_EINVAL;
   if (gamma && (((uintptr_t)gamma | (uintptr_t)beta) & 15)) return PM_EALIGN;
@@ -1931,6 +1932,7 @@ static int dec_linear_ksplit_impl(const float* x, int64_t ldx, const void* w, in
   if (M > 64 || K % 32) return PM_EUNSUPPORTED;
   if (k_split < 2 || k_split > 8 || K / 32 < k_split) return PM_EINVAL;
   if (ldx < K || ldw < K || ldx % 4 || ldw % 8) return PM_EALIGN;
+  if (ldx > 0x7fffffff || ldr > 0x7fffffff || ldo > 0x7fffffff) return PM_EINVAL;  // the kernel takes these strides as int
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)split_ws) & 15) return PM_EALIGN;
   if (mode == DL_PARTS && ((((uintptr_t)out) & 15) || ldo % 4 || ldr % 4)) return PM_EALIGN;
   if (ldo < N || (mode == DL_PLAIN && resid && ldr < N)) return PM_EINVAL;
@@ -2172,6 +2174,7 @@ static int dec_sample_topk_impl(const float* logits, int64_t ldl, int64_t V, int
                                 int64_t B, void* stream) {
   if (!logits || !pos_ptr || !prompt || !tok_cur || !tokens_out || !emb || !pos || !x || !ticket) return PM_EINVAL;
   if (V <= 0 || ldl < V || k < 1 || k > DS_MAXK || k > V || P <= 0 || B <= 0 || Ttot < P || d <= 0) return PM_EINVAL;
+  if (ldl > 0x7fffffff) return PM_EINVAL;  // the kernel takes the row stride as int
   if (d % 8) return PM_EUNSUPPORTED;
   if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)x) & 15) return PM_EALIGN;
   hipLaunchKernelGGL(dec_sample_topk_kernel<RAGGED>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, (int)ldl, (int)V,

@@ -622,8 +622,14 @@ static int linear_decide(const void* x, int64_t ldx, int64_t x_rows_per_batch, i
                       pm_linear_bf16_hyb_applies(M, N, K, act) && !(ln.row_out && act != PM_ACT_NONE);
   // (64 MI) x 256 tiles: LDS-DMA pieces of 8 whole rows off uniform row bases (M % 8 == 0, plain row addressing), epilogue
   // modes bias / LayerNorm-fold consumer / residual (+ row partials): a consumer with a residual stays on the 256 x 128 kernel
-  const bool tile_ok = wide_base && pm_linear_bf16_tile_applies(M, N, K, act) && M % 8 == 0 && x_rows_per_batch == 0 &&
-                       !(ln.stats && (resid || ln.row_out)) && !(ln.row_out && act != PM_ACT_NONE);
+  // Their global addresses are a uniform 64-bit row base plus a 32-bit BYTE lane offset: 7 rows of x, w and y (an 8-row piece),
+  // 15 rows of the residual block - a periodic residual is addressed off the operand's base, up to resid_period - 1 rows.
+  const int64_t lane_room = ((1LL << 32) - 2 * (K > N ? K : N) - 256) / 2;  // elements left for rows * ld
+  const int64_t resid_rows = resid_period ? (resid_period < M ? resid_period : M) - 1 : 15;
+  const bool tile_lanes_ok = ldx < lane_room / 7 && ldw < lane_room / 7 && ldy < lane_room / 7 &&
+                             (!resid || resid_rows == 0 || ldr < lane_room / resid_rows);
+  const bool tile_ok = wide_base && tile_lanes_ok && pm_linear_bf16_tile_applies(M, N, K, act) && M % 8 == 0 &&
+                       x_rows_per_batch == 0 && !(ln.stats && (resid || ln.row_out)) && !(ln.row_out && act != PM_ACT_NONE);
   int kernel;
   if (want_ln) {  // the LayerNorm fold lives in the persistent kernels' epilogues (row partials: the tile and 256 x 128 kernels)
     if (!staged_ok) return -PM_EUNSUPPORTED;

@@ -171,6 +171,7 @@ class Case:
     consumer: bool = False
     rows: bool = False          # want_row_stats
     strided: bool = False       # layernorm / row_stats: ldx > d
+    far: str = ""               # far family: "<x | w | resid | residp | y | win>:<2G | 4G | 8G>" - the operand placed far, the distance
 
     @property
     def id(self) -> str:
@@ -179,7 +180,7 @@ class Case:
         s += ("" if self.bias else "-nob") + (f"-r{self.resid}" if self.resid else "") + (f"-p{self.period}" if self.period else "")
         s += (f"-win{self.window}" if self.window else "") + ("-lnc" if self.consumer else "") + ("-rows" if self.rows else "")
         s += ("-ld" if self.strided else "") + (f"-{self.act}" if self.act != "none" else "")
-        return s
+        return s + (f"-{self.far.replace(':', '')}" if self.far else "")
 
     @property
     def fast_act(self) -> bool:
@@ -476,7 +477,7 @@ def build(case: Case) -> dict:
     if case.op in ("linear", "linear_f32"):
         xdt = torch.bfloat16 if case.op == "linear" else torch.float32
         nx = window_geometry(case)[2] if case.window else M * K
-        if fam == "exact":
+        if fam in ("exact", "far"):
             a = _exact_amp(K)
             xf = _ints(g, (nx,), a) * (torch.rand(nx, generator=g) < 0.5)
             w = _ints(g, (N, K), a)
@@ -503,7 +504,7 @@ def build(case: Case) -> dict:
         inp["bias"] = bias.float() if case.bias else None
         inp["resid"] = res.to(DT[case.resid]) if case.resid else None
         if case.consumer:
-            if fam == "exact":
+            if fam in ("exact", "far"):
                 mean = _ints(g, (M,), 4)
                 rstd = torch.ldexp(torch.ones(M), torch.randint(-1, 2, (M,), generator=g))
                 inp["s"] = _ints(g, (N,), 32)
@@ -745,7 +746,7 @@ def run(ops, case: Case, P: dict) -> dict:
     """The case through pytorch_models._hip.ops on the placed operands; y lands in P["y"]."""
     if case.op == "linear":
         if case.window:
-            rs, bs, _ = window_geometry(case)
+            rs, bs = P.get("window") or window_geometry(case)[:2]
             ops.linear_strided(P["xbuf"], M=case.M, K=case.K, row_stride=rs, rows_per_batch=case.window, batch_stride=bs, w=P["w"],
                                bias=P["bias"], act=case.act, resid=P["resid"], resid_period=case.period, out=P["y"])
             return dict(y=P["y"])
@@ -771,7 +772,7 @@ def run(ops, case: Case, P: dict) -> dict:
 def plan(ops, case: Case, P: dict) -> int:
     """pm_linear_bf16_plan for the call run() would make."""
     if case.window:
-        rs, bs, _ = window_geometry(case)
+        rs, bs = P.get("window") or window_geometry(case)[:2]
         return ops.linear_strided_plan(P["xbuf"], M=case.M, K=case.K, row_stride=rs, rows_per_batch=case.window, batch_stride=bs,
                                        w=P["w"], bias=P["bias"], act=case.act, resid=P["resid"], resid_period=case.period, out=P["y"])
     return ops.linear_plan(P["x"], P["w"], P["bias"], act=case.act, resid=P["resid"], out=P["y"], ln_stats=P.get("stats"),
@@ -912,7 +913,7 @@ def compare(case: Case, out: dict, ref: dict) -> tuple[float, int]:
         return float("inf"), -1
     r = ratio(y, ref["want"], ref["bound"])
     bad = 0
-    if case.family == "exact":
+    if case.family in ("exact", "far"):
         bad = int((bits(y) != bits(store(ref["want"], case.ydt))).sum())
         r = float("inf") if bad else 0.0
     if case.rows:
@@ -970,9 +971,188 @@ def judge(case: Case, inp: dict, ref: dict, runner, dev="cpu", margin: float = M
 
 
 def explain(rec: dict) -> str:
-    what = f"{rec['mismatches']} outputs differ from the exact result" if rec["family"] == "exact" else f"{rec['ratio']:.3f} x the bound (allowed {MARGIN})"
+    if rec.get("why"):
+        return f"{rec['id']}: {rec['why']}"
+    what = f"{rec['mismatches']} outputs differ from the exact result" if rec["family"] in ("exact", "far") else f"{rec['ratio']:.3f} x the bound (allowed {MARGIN})"
     return f"{rec['id']}: {what}; " + ", ".join(f"{k}={v}" for k, v in rec.items() if isinstance(v, bool))
 
 
 def figure(rec: dict) -> str:
     return f"FIGURE {rec['op']}{rec['kid'] or ''} {rec['family']} {rec['id']} ratio {rec['ratio']:.3f}"
+
+
+# --------------------------------------------------------------------------------------------------------------- far operands
+# DESIGN.md section 30.  The 256-wide GEMMs keep 32-bit offsets per operand and rely on linear_decide to keep every operand inside
+# them.  REACH states, per kernel id and operand, the largest quantity the kernel forms in 32 bits, read off the sources; a kernel
+# serves a call only while each stays below 2^32.  tests/test_linear_cases_cpu.py asks pm_linear_bf16_plan (host arithmetic on
+# made-up pointers) that no kernel id is returned for arguments beyond its reach - that covers bounds no allocation can reach -, and
+# the `far` family runs every bound that fits the arena on the GPU: exact-family operands, one of them a view into the poisoned
+# arena of tests/wrapper_cases.py with its last row (last batch, last period row) just past 2^31, 2^32 bytes - or, where a kernel's
+# reach lies there, 2^33 bytes = 2^32 bf16 elements.  A refusal is a pass; whatever runs must EQUAL want.to(out dtype) whichever
+# kernel took it (the dispatcher may move a case it cannot address: `planned` goes into the record, it is not asserted), leave every
+# sentinel of the y buffer alone and leave the arena outside the view all poison.
+#
+#   ids 1, 2 (linear_bf16.hip)   every offset is int64 ((int64_t)gm * ldx + ..., (int64_t)m * ldy + n, ...): no 32-bit reach
+#   id 3 (linear_bf16_wide.hip)  xoff / woff are uint32 ELEMENT offsets of 16-byte chunks: (M - 1) ldx + K - 8 - the window form:
+#                                (M / R - 1) batch_stride + (R - 1) ldx + K - 8 -, (N - 1) ldw + K - 8; resid and y are int64
+#   ids 6, 7 (linear_bf16_tile.hip)  uniform 64-bit row bases plus uint32 BYTE lane offsets: a piece is 8 rows, so x and w reach
+#                                7 * 2 ld + (K / 64 - 1) * 128 + 127; the residual block is 16 rows off a 64-bit base,
+#                                15 * 2 ldr + 2 (N - 8) + 15, and a periodic residual is addressed off the operand's base,
+#                                (min(P, M) - 1) * 2 ldr + 2 (N - 8) + 15; y: 7 * 2 ldy + 7 * 16 + 15
+LIMIT32 = 1 << 32
+FAR_DIST = {"2G": 1 << 31, "4G": 1 << 32, "8G": 1 << 33}
+
+
+def reach(kid: int, M: int, N: int, K: int, ldx: int, ldw: int, ldr: int = 0, ldy: int = 0, period: int = 0, window: int = 0,
+          batch_stride: int = 0) -> dict:
+    """operand -> the largest quantity kernel `kid` forms in 32 bits for it (module comment above); {} for ids 1 and 2"""
+    if kid == 3:
+        x = (M // window - 1) * batch_stride + (window - 1) * ldx + K - 8 if window else (M - 1) * ldx + K - 8
+        return dict(x=x, w=(N - 1) * ldw + K - 8)
+    if kid in (6, 7):
+        r = dict(x=14 * ldx + (K // 64 - 1) * 128 + 127, w=14 * ldw + (K // 64 - 1) * 128 + 127, y=14 * ldy + 127)
+        if ldr:
+            r["resid"] = ((min(period, M) - 1) if period else 15) * 2 * ldr + 2 * (N - 8) + 15
+        return r
+    return {}
+
+
+FAR_SHAPE = {1: (136, 136, 64), 2: (4096, 8, 64), 3: (4104, 8, 64), 6: (4096, 8, 64), 7: (4096, 8, 64)}  # the smallest each id lists
+FAR_WINDOW = {1: (144, 48), 2: (4104, 1026), 3: (4104, 1026), 6: (4104, 1026), 7: (4104, 1026)}     # (M, rows per batch)
+
+
+def _far_cases() -> list[Case]:
+    c = []
+    for kid in (1,) + FORCED_IDS:
+        M, N, K = FAR_SHAPE[kid]
+        for which in ("x", "w", "resid", "y"):
+            for d in ("2G", "4G") + (("8G",) if kid == 3 and which in ("x", "w") else ()):  # id 3's reach: 2^32 elements
+                c.append(_lin(kid, "far", M, N, K, resid="bf16", far=f"{which}:{d}"))
+        for d in ("4G",) + (("8G",) if kid == 3 else ()):
+            c.append(_lin(kid, "far", FAR_WINDOW[kid][0], N, K, window=FAR_WINDOW[kid][1], resid="bf16", far=f"win:{d}"))
+        for per in (2, 3):  # ids 6 / 7: the periodic row offset (mm % P) * (ldr * 2) was formed in 32 bits
+            c.append(_lin(kid, "far", M, N, K, resid="bf16", period=per, far="residp:4G"))
+    return c
+
+
+FAR_CASES = _far_cases()
+FAR_DEFAULT = [c for c in FAR_CASES if not c.forced]
+FAR_FORCED = {k: [c for c in FAR_CASES if c.forced and c.kid == k] for k in FORCED_IDS}
+assert len({c.id for c in FAR_CASES}) == len(FAR_CASES)
+
+
+def far_geometry(case: Case) -> tuple[str, tuple, tuple]:
+    """(operand, shape, strides in elements) of the far view of a case"""
+    import wrapper_cases as WC
+    which, d = case.far.split(":")
+    if which == "win":
+        rs, _, _ = window_geometry(case)
+        nb, seg = case.M // case.window, (case.window - 1) * rs + case.K
+        return "xbuf", (nb, seg), (WC.far_stride(nb, 2, FAR_DIST[d]), 1)
+    rows, cols = {"x": (case.M, case.K), "w": (case.N, case.K), "resid": (case.M, case.N), "residp": (case.period, case.N),
+                  "y": (case.M, case.N)}[which]
+    return which.replace("residp", "resid"), (rows, cols), (WC.far_stride(rows, 2, FAR_DIST[d]), 1)
+
+
+def far_lds(case: Case) -> dict:
+    """the strides the far call passes, for reach(): the far one from far_geometry, the others packed"""
+    name, shape, st = far_geometry(case)
+    g = dict(M=case.M, N=case.N, K=case.K, ldx=case.K, ldw=case.K, ldr=case.N, ldy=case.N, period=case.period, window=case.window)
+    if case.window:
+        g["ldx"], g["batch_stride"] = window_geometry(case)[:2]
+    g[{"x": "ldx", "w": "ldw", "resid": "ldr", "y": "ldy", "xbuf": "batch_stride"}[name]] = st[0]
+    return g
+
+
+def place_far(case: Case, inp: dict, arena, dev="cpu", touch: bool = True) -> dict:
+    """place() with the one far operand a view into `arena`; touch=False builds the views without writing them (the CPU stage
+    checks the arithmetic and maps nothing)."""
+    import wrapper_cases as WC
+    P = place(case, inp, dev)
+    name, shape, st = far_geometry(case)
+    view = arena.view(shape, st, torch.bfloat16)
+    if name == "xbuf":
+        rs, bs0, _ = window_geometry(case)
+        src = torch.stack([inp["xbuf"][b * bs0:b * bs0 + shape[1]] for b in range(shape[0])])
+        P["xbuf"] = arena.view(((shape[0] - 1) * st[0] + shape[1],), (1,), torch.bfloat16)
+        P["window"] = (rs, st[0])
+    else:
+        src = torch.zeros(shape, dtype=torch.bfloat16) if name == "y" else inp[name]
+        P[name] = view
+        if name == "y":
+            del P["y_buf"], P["y_geom"]
+    assert tuple(src.shape) == tuple(shape) and src.dtype == torch.bfloat16
+    P["far_view"] = view
+    P["far_case"] = WC.FarCase("far:" + case.far.split(":")[1], 0, view, tuple(st), 2, src.numel(), 32)
+    if touch:
+        view.copy_(src.to(dev))
+    return P
+
+
+def judge_far(case: Case, inp: dict, ref: dict, ops, arena, dev="cuda") -> dict:
+    """One far case as a record: refused (a pass: y and the arena untouched, and the plan says so too) or run - then y equals
+    want.to(out dtype) bit for bit, the sentinels of the y buffer and the arena outside the view are as they were."""
+    import wrapper_cases as WC
+    P = place_far(case, inp, arena, dev)
+    rec = dict(id=case.id, op=case.op, kid=case.kid, family=case.family, far=case.far, ratio=0.0, mismatches=0)
+    gate = arena.holds(P["far_case"])
+    if gate:  # never run what the arena cannot contain
+        arena.erase(P["far_view"])
+        return dict(rec, ok=False, why="; ".join(gate))
+    rec["planned"] = plan(ops, case, P)
+    try:
+        out, rec["refused"] = run(ops, case, P), False
+        rec["ratio"], rec["mismatches"] = compare(case, out, ref)
+    except (ValueError, RuntimeError) as e:
+        if WC.is_fault(e):
+            raise
+        rec["refused"], rec["refusal"] = True, str(e)[:200]
+        rec["y_untouched"] = bool((P["y"].cpu().float() == 0).all())
+    rec["sentinel"] = sentinels_intact(case, P)
+    arena.erase(P["far_view"])
+    at = arena.dirty()
+    rec["arena_clean"] = at is None
+    if at is not None:
+        rec["arena_first"] = at - arena.base
+        arena.words.fill_(WC.POISON32)
+    rec["plan_agrees"] = (rec["planned"] < 0) == rec["refused"]
+    rec["ok"] = bool(rec["mismatches"] == 0 and all(v for k, v in rec.items() if k in ("sentinel", "arena_clean", "plan_agrees", "y_untouched")))
+    rec["ratio"] = 0.0 if rec["mismatches"] == 0 else 1e300
+    return rec
+
+
+# ---- the reach table against the dispatcher: pm_linear_bf16_plan on made-up aligned pointers (it never dereferences)
+def plan_args(M, N, K, ldx, ldw, ldr=0, ldy=0, period=0, window=0, batch_stride=0) -> tuple:
+    """the arguments of pm_linear_bf16_plan for a bf16 call with a bias and - where ldr is given - a bf16 residual"""
+    p = lambda i: (1 << 40) + (i << 36)  # noqa: E731
+    return (p(0), ldx, window, batch_stride, p(1), ldw, p(2), p(3) if ldr else None, ldr, 0, period if ldr else 0, p(4), ldy or N, 0,
+            M, N, K, 0, None, None, None, None, 0)
+
+
+def reach_probes(kid: int) -> dict:
+    """name -> (geometry just beyond kernel `kid`'s reach in one operand, that operand).  The far stride is the smallest multiple
+    of 8 at which reach() passes 2^32; every other stride is packed.  "base" is the same call with every stride packed."""
+    M, N, K = FAR_SHAPE[kid]
+    Mw, R = FAR_WINDOW[kid]
+    base = dict(M=M, N=N, K=K, ldx=K, ldw=K, ldr=N, ldy=N)
+    forms = {"x": (base, "ldx", "x"), "w": (base, "ldw", "w"), "resid": (base, "ldr", "resid"), "y": (base, "ldy", "y"),
+             "residp2": (dict(base, period=2), "ldr", "resid"), "residp3": (dict(base, period=3), "ldr", "resid"),
+             "win": (dict(base, M=Mw, window=R, ldx=16, batch_stride=(R - 1) * 16 + K + 40), "batch_stride", "x")}
+    out = {"base": (base, None)}
+    for name, (g, key, operand) in forms.items():
+        if operand not in reach(kid, **g) or (name == "win" and kid != 3):
+            continue
+        lo, hi = g[key], 1 << 40
+        while hi - lo > 8:  # reach() grows with the stride: bisect over multiples of 8
+            mid = (lo + hi) // 16 * 8
+            lo, hi = (lo, mid) if reach(kid, **dict(g, **{key: mid}))[operand] >= LIMIT32 else (mid, hi)
+        out[name] = (dict(g, **{key: hi}), operand)
+    return out
+
+
+def reach_fits_arena(g: dict, operand: str, after: int) -> bool:
+    """the operand of a probe, as far as the kernel reads it, ends within `after` bytes of its base"""
+    rows = {"x": g["M"], "w": g["N"], "y": g["M"], "resid": g.get("period") or g["M"]}[operand]
+    if g.get("window"):
+        return ((g["M"] // g["window"] - 1) * g["batch_stride"] + g["window"] * 16 + g["K"]) * 2 <= after
+    return ((rows - 1) * g[{"x": "ldx", "w": "ldw", "y": "ldy", "resid": "ldr"}[operand]] + max(g["N"], g["K"])) * 2 <= after

@@ -3,6 +3,10 @@
     python linear_child.py plan <id>        host only: pm_linear_bf16_plan for every case forced to <id>; prints {case id: kernel} as JSON
     python linear_child.py run <id> <out>   on the GPU: asserts the plan of every placement, runs linear_cases.judge on every case forced to <id>, appends
                                             one JSON record per case to <out> (flushed per case, so a crash leaves what was done)
+    python linear_child.py reach <id>       host only: pm_linear_bf16_plan on linear_cases.reach_probes(<id>), made-up pointers; prints {probe: kernel} as JSON
+    python linear_child.py far <id> <out>   on the GPU: linear_cases.judge_far on every far case forced to <id>, one poisoned arena for all of them; a
+                                            record per case as `run` writes them, with `planned` RECORDED, not asserted: the dispatcher may move a case
+                                            it cannot address
 Started by tests/test_linear_cases_cpu.py and tests/test_hip_linear_adversarial.py with sys.executable; not a test module."""
 import json
 import os
@@ -35,7 +39,24 @@ def main() -> int:
                 got[case.id] = got[case.id] if poisoned == got[case.id] else -100 - poisoned
         print(json.dumps(got))
         return 0
+    if mode == "reach":
+        from pytorch_models._hip import lib
+
+        print(json.dumps({name: int(lib().pm_linear_bf16_plan(*LC.plan_args(**g))) for name, (g, _) in LC.reach_probes(kid).items()}))
+        return 0
     assert torch.cuda.is_available()
+    if mode == "far":
+        import wrapper_cases as WC
+
+        arena = WC.Arena(WC.Arena.bytes_for(32), "cuda")
+        with open(sys.argv[3], "a") as f:
+            for case in LC.FAR_FORCED[kid]:
+                inp = LC.build(case)
+                rec = LC.judge_far(case, inp, LC.reference(case, inp), ops, arena)  # a HIP error ends the child: exit code 1, no further case
+                f.write(json.dumps(rec) + "\n")
+                f.flush()
+                print(LC.figure(rec), "planned", rec.get("planned"), "refused" if rec.get("refused") else "ran", flush=True)
+        return 0
     with open(sys.argv[3], "a") as f:
         for case in LC.FORCED_CASES[kid]:
             inp = LC.build(case)

@@ -32,6 +32,11 @@ LayerNorm-fold numerics contract".
     row_stats          f32     -       0.020   0.001   -       -
 With a bf16 output the half-ulp store term dominates the bound and a correct store reaches it; the f32 rows show the arithmetic
 alone.  174 tests, 16 s (12 s of it the four child processes).  The assertions do not depend on these numbers.
+
+Far operands (linear_cases, "far operands"): 58 more tests, 13 s (10 s of it four more children).  Exact-family
+operands with one operand a view into a poisoned 16 GiB arena, its last row - last batch of the window form, last row of a periodic
+residual - just past 2^31 / 2^32 bytes, and 2^33 where kernel id 3's reach lies.  Refused (nothing written), or equal to want bit for
+bit with sentinels and arena intact, whichever kernel the dispatcher chose: `planned` is recorded, not asserted.
 """
 import json
 import os
@@ -124,6 +129,66 @@ def test_forced_kernel(forced, case):
     assert rec is not None, forced.get(f"broken{case.kid}", f"{case.id}: the child of kernel id {case.kid} left no record")
     print(LC.figure(rec))
     assert rec["planned"] == case.kid, f"{case.id}: PM_GEMM_KERNEL={case.kid} reached kernel {rec['planned']}"
+    assert rec["ok"], LC.explain(rec)
+
+
+# ---------------------------------------------------------------------------------------------------------------- far operands
+# linear_cases, "far operands": exact-family operands, one of them a view into a poisoned arena with its last row (batch, period
+# row) just past 2^31 / 2^32 bytes - 2^33 where kernel id 3's reach lies.  Refused, or bit-equal to want whichever kernel ran.
+@pytest.fixture(scope="module")
+def far_arena(forced):  # behind the forced children: one 16 GiB allocation at a time
+    import wrapper_cases as WC
+
+    assert not FAULT, f"not run: {FAULT[0]}"
+    need = WC.Arena.bytes_for(32)
+    free, _ = torch.cuda.mem_get_info()
+    if free < need + (2 << 30):
+        pytest.skip(f"far operands need an arena of {need} bytes plus 2 GiB: {free} bytes of device memory are free")
+    a = WC.Arena(need, "cuda")
+    yield a
+    del a.words
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("case", LC.FAR_DEFAULT, ids=lambda c: c.id)
+def test_far_default_dispatch(ops, far_arena, case):
+    inp = LC.build(case)
+    rec = _on_gpu(case.id, lambda: LC.judge_far(case, inp, LC.reference(case, inp), ops, far_arena))
+    print(LC.figure(rec), "planned", rec.get("planned"), "refused" if rec.get("refused") else "ran")
+    assert rec["ok"], LC.explain(rec)
+
+
+@pytest.fixture(scope="module")
+def far_forced(tmp_path_factory, forced, far_arena):
+    """as `forced`, for the far cases: one child per kernel id, each with an arena of its own"""
+    out = {}
+    for kid in LC.FORCED_IDS:
+        if FAULT:
+            out[kid] = f"not started: {FAULT[0]}"
+            continue
+        path = str(tmp_path_factory.mktemp("linear_far") / f"id{kid}.jsonl")
+        try:
+            r = subprocess.run([sys.executable, os.path.join(HERE, "linear_child.py"), "far", str(kid), path],
+                               env=dict(os.environ, PM_GEMM_KERNEL=str(kid)), capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+            rc, log = r.returncode, r.stdout + r.stderr[-3000:]
+        except subprocess.TimeoutExpired as e:
+            rc, log = None, f"{e.stdout or ''}"
+        print(log)
+        out[kid] = {d["id"]: d for d in map(json.loads, open(path).read().splitlines())} if os.path.exists(path) else {}
+        if rc != 0:  # a hang, a signal or an exception - a HIP error included: nothing more of this file touches the GPU
+            out[f"broken{kid}"] = f"the far child of kernel id {kid} " + ("timed out" if rc is None else f"ended with {rc}") + \
+                f" after {len(out[kid])} cases: {log[-1500:]}"
+            FAULT.append(out[f"broken{kid}"])
+    return out
+
+
+@pytest.mark.parametrize("case", [c for k in LC.FORCED_IDS for c in LC.FAR_FORCED[k]], ids=lambda c: c.id)
+def test_far_forced_kernel(far_forced, case):
+    recs = far_forced[case.kid]
+    assert not isinstance(recs, str), recs
+    rec = recs.get(case.id)
+    assert rec is not None, far_forced.get(f"broken{case.kid}", f"{case.id}: the far child of kernel id {case.kid} left no record")
+    print(LC.figure(rec), "planned", rec.get("planned"), "refused" if rec.get("refused") else "ran")
     assert rec["ok"], LC.explain(rec)
 
 

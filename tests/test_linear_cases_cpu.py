@@ -3,7 +3,12 @@
 makes (linear_cases.judge, the same function) at MARGIN 1.0; every defect in linear_cases.MUTANTS fails at least one case; the case
 lists reach every path they are named for; the exact family's preconditions hold; and, with the library built, the host-only
 pm_linear_bf16_plan sends every case to the kernel it is listed under - unforced for the default-dispatch cases, in one child
-process per PM_GEMM_KERNEL value for the forced ones (the children call the query only: nothing is launched)."""
+process per PM_GEMM_KERNEL value for the forced ones (the children call the query only: nothing is launched).
+
+Far operands (linear_cases, "far operands"): every far case keeps the exact family's preconditions and satisfies the arena's
+containment rule as pure arithmetic (no memory is mapped); the reach table is asserted against pm_linear_bf16_plan - for arguments
+just beyond a kernel id's reach in one operand the plan never returns that id, forced or not -; and every reach bound whose operand
+fits the arena has a far case that crosses it, so the table is tied to the kernels on the GPU and not only to itself."""
 import json
 import os
 import subprocess
@@ -137,3 +142,75 @@ def test_forced_cases_dispatch_to_their_kernel(kid):
     assert set(got) == {c.id for c in LC.FORCED_CASES[kid]}
     wrong = {k: v for k, v in got.items() if v != kid}
     assert not wrong, f"PM_GEMM_KERNEL={kid} does not reach kernel {kid} on: {wrong}"
+
+
+# --------------------------------------------------------------------------------------------------------------- far operands
+@pytest.fixture(scope="module")
+def far_arena():
+    import wrapper_cases as WC
+    a = WC.Arena(WC.Arena.bytes_for(32), "cpu", poisoned=False)  # torch.empty maps lazily, and nothing below writes to it
+    yield a
+    del a.words
+
+
+@pytest.mark.parametrize("case", LC.FAR_CASES, ids=lambda c: c.id)
+def test_far_case_is_exact_and_contained(case, far_arena):
+    inp = LC.build(case)
+    pre = LC.exact_preconditions(case, inp, LC.reference(case, inp))
+    assert pre["limit"] < 2 ** 24 and pre["integral"] and pre["share"] >= 0.10, pre
+    name, shape, st = LC.far_geometry(case)
+    assert (shape[0] - 1) * st[0] * 2 > LC.FAR_DIST[case.far.split(":")[1]] and st[0] % 64 == 0 and st[0] >= shape[1], (name, shape, st)
+    P = LC.place_far(case, inp, far_arena, touch=False)
+    assert not far_arena.holds(P["far_case"]), far_arena.holds(P["far_case"])
+    assert P["far_view"].data_ptr() == far_arena.words.data_ptr() + far_arena.base and P["far_view"].stride() == st
+    assert LC.abi_refusal(case, P) is None
+    assert LC.plan(ops_module(), case, P) != 0  # the host-only query takes the far call: a kernel id, or minus an error code
+
+
+def ops_module():
+    from pytorch_models._hip import ops
+
+    return ops
+
+
+def _reach_violations(kid: int, got: dict) -> list[str]:
+    bad = [f"{name}: pm_linear_bf16_plan returns kernel {kid} for {g}, beyond its reach in {operand} "
+           f"({LC.reach(kid, **g)[operand]} >= 2^32)" for name, (g, operand) in LC.reach_probes(kid).items()
+           if operand and got[name] == kid]
+    for name, (g, operand) in LC.reach_probes(kid).items():
+        assert operand is None or LC.reach(kid, **g)[operand] >= LC.LIMIT32
+    return bad
+
+
+@pytest.mark.parametrize("kid", (3, 6, 7))
+def test_plan_never_returns_a_kernel_beyond_its_reach(kid):
+    """forced (a child with PM_GEMM_KERNEL=<id>: the packed base call must reach the id, so the probes are live) and unforced"""
+    assert _lib_built(), "build the library first (the reach check needs pm_linear_bf16_plan)"
+    from pytorch_models._hip import lib
+
+    env = dict(os.environ, PM_GEMM_KERNEL=str(kid))
+    r = subprocess.run([sys.executable, os.path.join(HERE, "linear_child.py"), "reach", str(kid)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    forced = json.loads(r.stdout.strip().splitlines()[-1])
+    assert forced["base"] == kid, f"PM_GEMM_KERNEL={kid} does not reach kernel {kid} on the probes' packed base call: {forced['base']}"
+    free = {name: int(lib().pm_linear_bf16_plan(*LC.plan_args(**g))) for name, (g, _) in LC.reach_probes(kid).items()}
+    bad = _reach_violations(kid, forced) + _reach_violations(kid, free)
+    assert not bad, "\n".join(bad)
+
+
+def test_every_reach_bound_that_fits_the_arena_has_a_far_case():
+    import wrapper_cases as WC
+    after = WC.Arena.bytes_for(32) // 2
+    lacking = []
+    for kid in (3, 6, 7):
+        for name, (g, operand) in LC.reach_probes(kid).items():
+            if operand is None or not LC.reach_fits_arena(g, operand, after):
+                continue
+            form = lambda c: ("win" if c.window else f"residp{c.period}" if c.period else c.far.split(":")[0])  # noqa: E731
+            hit = [c for c in LC.FAR_FORCED[kid] if form(c) == name and c.far.split(":")[0] in (name, "residp", "win")
+                   and LC.reach(kid, **LC.far_lds(c))[operand] >= LC.LIMIT32]
+            if not hit:
+                lacking.append((kid, name))
+    assert not lacking, f"reach bounds that fit the arena and have no far case crossing them: {lacking}"
+    assert {(k, n) for k in (3, 6, 7) for n, (g, o) in LC.reach_probes(k).items() if o and LC.reach_fits_arena(g, o, after)} >= \
+        {(3, "x"), (3, "w"), (6, "w"), (7, "w"), (6, "residp2"), (7, "residp3")}

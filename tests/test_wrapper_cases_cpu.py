@@ -13,7 +13,16 @@ the ``id`` of what it is given and does not raise.  Canonical operands are CPU t
     the canonical dtype (offset, rank) must launch with the canonical integers; any other one must change the launch - a
     stride, a dtype code, a size, or a copy in place of the operand's own pointer.  Accepted with the canonical integers and
     its own pointer = the kernel reads data_ptr() as packed: a hole.
-``python tests/test_wrapper_cases_cpu.py`` prints the accepted (wrapper, operand, variant) triples."""
+Far operands (wrapper_cases.check_row_far): every operand with a ``rowpad`` / ``rowpad0`` variant gets its
+far variants, as views into one lazily mapped arena of which only the views are touched.  Asserted:
+  * completeness and containment (pure arithmetic on base, strides and arena size: the gate in front of any GPU run);
+  * refusals happen with zero recorded launches and leave the in-place operands alone;
+  * the audit: an accepted far operand reaches the C call with its own pointer and the far stride among the integers (or as a
+    copy); the width audit: every recorded integer of magnitude >= 2^31 sits at a position SIGNATURES declares 64 bits wide
+    (ctypes masks an int given to a c_int parameter without raising);
+  * the driver has teeth: the same checker at a 16-bit width over a tiny arena reports each of five toy kernels with one
+    planted 16-bit defect, and passes their wide twin.
+``python tests/test_wrapper_cases_cpu.py`` prints the accepted (wrapper, operand, variant) triples, then the far ones."""
 import ctypes
 import inspect
 import os
@@ -27,7 +36,7 @@ for _p in (_HERE, os.path.join(os.path.dirname(_HERE), "pytorch-models_amd")):  
     if _p not in sys.path:
         sys.path.insert(0, _p)
 import wrapper_cases as WC  # noqa: E402
-from pytorch_models._hip import decode_plan, ops  # noqa: E402
+from pytorch_models._hip import SIGNATURES, decode_plan, ops  # noqa: E402
 
 torch.set_grad_enabled(False)
 CPU = torch.device("cpu")
@@ -92,6 +101,29 @@ class Recorder:
         if not plain and got == self.canon:
             return ["HOLE: accepted, and the launch is the canonical one: the kernel reads data_ptr() as packed " + v.tag.split(":")[0]]
         return []
+
+    def end_far(self, r, path, c, kw: dict, refused: bool) -> list[str]:
+        """the hook of wrapper_cases.check_row_far"""
+        if refused:
+            return [f"refused after {len(self.launches)} launches"] if self.launches else []
+        bad, ptr, far = [], c.tensor.data_ptr(), c.strides[c.dim]
+        flat = [(name, [int(v or 0) for a in args for v in (a if isinstance(a, ctypes.Array) else [a])
+                        if isinstance(v, int) and not isinstance(v, bool) or v is None]) for name, args in self.launches]
+        if any(ptr in ints for _, ints in flat) and not any(ptr in ints and far in ints for _, ints in flat):
+            bad.append(f"HOLE: accepted with its own pointer, and no launch that takes it is told the stride {far}")
+        return bad + width_audit(self.launches)
+
+
+def width_audit(launches) -> list[str]:
+    """every recorded integer argument of magnitude >= 2^31 must be declared 64 bits wide at its position"""
+    bad = []
+    for name, args in launches:
+        types = SIGNATURES[name][0]
+        for i, a in enumerate(args):
+            if isinstance(a, int) and not isinstance(a, bool) and abs(a) >= 2 ** 31 and \
+                    types[i] not in (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64):
+                bad.append(f"HOLE: {name} argument {i} = {a} is declared {types[i].__name__}: ctypes masks it without raising")
+    return bad
 
 
 def _delta(a, b) -> str:
@@ -198,6 +230,123 @@ def test_variants_are_refused_before_a_launch_or_reach_it_whole(rid, rec):
     assert not problems, "\n".join([f"{len(problems)} problems:"] + problems)
 
 
+# ------------------------------------------------------------------------------------------------------------ far operands
+@pytest.fixture(scope="module")
+def arena():
+    a = WC.Arena(WC.Arena.bytes_for(32), CPU, poisoned=False)  # torch.empty maps lazily: only the views are ever touched
+    yield a
+    del a.words
+
+
+def test_every_padded_dimension_gets_its_far_variants(arena):
+    n = 0
+    for r in WC.ALL_FAR_ROWS.values():
+        for path, t in WC.operands(r.build(CPU)):
+            cs = WC.far_cases(t, arena)
+            got = [(c.tag, c.dim) for c in cs]
+            assert len(got) == len(set(got)) and set(got) == WC.applicable_far(t), (r.id, path, got, WC.applicable_far(t))
+            for c in cs:
+                n += 1
+                where = (r.id, WC.path_name(path), c.name)
+                assert not arena.holds(c), (where, arena.holds(c))
+                assert sum(c.needs()) <= WC.ARENA_CAP, where
+                v, last = c.tensor, (t.shape[c.dim] - 1) * c.strides[c.dim] * c.item
+                assert v.shape == t.shape and v.stride() == c.strides and v.data_ptr() == arena.words.data_ptr() + arena.base, where
+                assert last > WC.far_boundary(c.tag, c.item) and c.strides[c.dim] % WC.FAR_ALIGN == 0, where
+                assert last - WC.far_boundary(c.tag, c.item) <= (t.shape[c.dim] - 1) * WC.FAR_ALIGN * c.item, (where, "not just past")
+                assert all(s == p for d, (s, p) in enumerate(zip(c.strides, WC._packed(t.shape))) if d != c.dim), where
+                assert ops._apart(v), where
+    assert n > 300, n
+
+
+@pytest.mark.parametrize("rid", list(WC.ALL_FAR_ROWS))
+def test_far_variants_are_refused_before_a_launch_or_reach_it_whole(rid, rec, arena):
+    problems, _, _ = WC.check_row_far(ops, WC.ALL_FAR_ROWS[rid], CPU, arena, compare=False, hook=rec)
+    assert not problems, "\n".join([f"{len(problems)} problems:"] + problems)
+
+
+def test_width_audit_sees_a_narrow_parameter():
+    assert width_audit([("pm_geglu", (1 << 40, 2 ** 31 + 64, 1 << 41, 8, 2, 4, 0))]) == []
+    bad = width_audit([("pm_layernorm", (1 << 40, 64, 2 ** 31 + 64, None, None, 1e-5, 1 << 41, 64, 0, 2, 64, 0))])
+    assert len(bad) == 1 and "argument 2" in bad[0] and "c_int" in bad[0], bad
+
+
+# ---- teeth: toy kernels at a 16-bit width over a tiny arena, through the same driver
+TOY_W = 16
+
+
+def _toy(defect: str):
+    """y[m, :] = 2 * x[m, :] + 1 over raw words of the arena, offsets formed as a C launcher would form them; ``defect`` names
+    the one place where the arithmetic is ``TOY_W`` bits wide"""
+    def row(t, off, K):  # K floats at byte address data_ptr() + off, as a kernel sees them
+        return torch.frombuffer((ctypes.c_float * K).from_address(t.data_ptr() + off), dtype=torch.float32)
+
+    def fn(x, out):
+        (M, K), it = x.shape, x.element_size()
+        ldx, ldo = x.stride(0), out.stride(0)
+        if ldx < K or ldo < K:
+            raise ValueError("toy: rows overlap")
+        for m in range(M):
+            xo, oo = m * ldx * it, m * ldo * it
+            if defect == "int32 elements":
+                xo = WC.wrap(m * ldx, TOY_W, True) * it
+            elif defect == "uint32 bytes":
+                xo = WC.wrap(m * ldx * it, TOY_W, False)
+            elif defect == "int32 bytes":
+                xo = WC.wrap(m * ldx * it, TOY_W, True)
+            elif defect == "(int)ld":
+                xo = m * WC.wrap(ldx, TOY_W, True) * it
+            elif defect == "wrapped write":
+                oo = WC.wrap(m * ldo * it, TOY_W, False)
+            row(out, oo, K).copy_(row(x, xo, K) * 2 + 1)
+        return None
+    return fn
+
+
+def _toy_row(arena):
+    def build(g):
+        return dict(x=g.f(2, 8), out=g.z(2, 8))
+    return WC.Row("toy", "toy", lambda dev, seed=0: build(WC.Gen(dev, WC.SEED)), ("out",))
+
+
+# defect (named at its 32-bit width; planted at TOY_W bits) -> the variants that must report it, from the arithmetic alone: with two
+# f32 rows the element offset and the stride itself pass 2^(w-1) only at far:2Ge; a byte offset passes 2^w from far:4G on, and as a
+# signed register it is wrong from 2^(w-1) on - negative at far:2G, short by 2^w behind it
+TOY_DEFECTS = {"int32 elements": ("x far:2Ge@0",), "uint32 bytes": ("x far:4G@0", "x far:2Ge@0"), "int32 bytes": ("x far:2G@0", "x far:4G@0", "x far:2Ge@0"),
+               "(int)ld": ("x far:2Ge@0",), "wrapped write": ("out far:4G@0", "out far:2Ge@0")}
+
+
+@pytest.mark.parametrize("defect", [None] + list(TOY_DEFECTS))
+def test_far_driver_reports_each_planted_narrow_offset(defect):
+    import types
+    toy_arena = WC.Arena(WC.Arena.bytes_for(TOY_W, slack=4096), CPU)
+    problems, acc, ref = WC.check_row_far(types.SimpleNamespace(toy=_toy(defect)), _toy_row(toy_arena), CPU, toy_arena, compare=True,
+                                          width=TOY_W)
+    assert len(acc) == 6 and not ref, (acc, ref)  # x and out at the three distances
+    if defect is None:
+        assert not problems, problems
+        return
+    hit = {p.split(": ")[0].replace("toy ", "", 1) for p in problems}
+    assert hit == set(TOY_DEFECTS[defect]), (defect, problems)
+    if defect == "wrapped write":
+        assert any("wrote outside the view" in p for p in problems), problems
+
+
+def far_triples():
+    """(accepted, refused, problems) of the far variants on the CPU stage"""
+    mp = pytest.MonkeyPatch()
+    try:
+        r = _install(mp)
+        a = WC.Arena(WC.Arena.bytes_for(32), CPU, poisoned=False)
+        acc, ref, probs = [], [], []
+        for row in WC.ALL_FAR_ROWS.values():
+            p, x, y = WC.check_row_far(ops, row, CPU, a, compare=False, hook=r)
+            acc, ref, probs = acc + x, ref + y, probs + p
+        return acc, ref, probs
+    finally:
+        mp.undo()
+
+
 def accepted_triples() -> list:
     """the accepted set: every (row, operand, variant) that reaches a launch on the CPU stage"""
     mp = pytest.MonkeyPatch()
@@ -215,3 +364,10 @@ def accepted_triples() -> list:
 if __name__ == "__main__":
     for (rid, operand, tag), verdict in accepted_triples():
         print(f"{rid:28s} {operand:18s} {tag:16s} {verdict}")
+    acc, ref, probs = far_triples()
+    for kind, ts in (("accepted", acc), ("refused", ref)):
+        for rid, operand, tag in ts:
+            print(f"{rid:28s} {operand:18s} {tag:16s} {kind}")
+    print(f"far: {len(acc) + len(ref)} generated, {len(acc)} accepted, {len(ref)} refused, {len(probs)} problems")
+    for p in probs:
+        print("  ", p)

@@ -833,3 +833,247 @@ def check_row(ops, r: Row, dev, compare: bool, hook=None) -> tuple[list[str], li
             if bad:
                 problems.append(f"{where}: accepted but {bad} differ from the contiguous call")
     return problems, accepted
+
+
+# ------------------------------------------------------------------------------------------- far operands
+# An operand whose leading stride carries its last row past 2^31 bytes, 2^32 bytes or 2^31 elements from its base: the three
+# distances at which an int32 byte offset, a uint32 byte offset and an int32 element offset stop holding the truth.  Such an
+# operand is refused before the first launch, or the call returns the bits of the same call on a compact copy and writes nowhere
+# else.  Every far operand is a view into one ARENA, poisoned with POISON32 (NaN as bf16 and as f32, absurd as an integer) and
+# based in its middle, sized so that any single ``width``-bit misreading of the far term (``misreadings``) stays inside it: a
+# wrap poisons the result, it does not leave the allocation.  All arithmetic is written against ``width`` so that the CPU stage
+# can run the same checker at 16 bits over a few hundred kilobytes, with toy kernels that hold one planted defect each.
+POISON32 = 0x7FC07FC0
+FAR_TAGS = ("far:2G", "far:4G", "far:2Ge")
+FAR_ALIGN = 64                    # elements: every alignment a canonical operand has survives a stride that is a multiple of it
+ARENA_CAP = 17 << 30              # bytes; a case that asks for more is a bug of the generator
+
+
+def wrap(v: int, width: int, signed: bool) -> int:
+    """``v`` as a ``width``-bit integer register holds it"""
+    v &= (1 << width) - 1
+    return v - (1 << width) if signed and v >> (width - 1) else v
+
+
+def far_boundary(tag: str, item: int, width: int = 32) -> int | None:
+    """bytes from the base that the last index must pass; None where the tag coincides with a byte distance (bf16 at 2^31
+    elements is 2^32 bytes) or does not apply (elements wider than 4 bytes)"""
+    half, full = 1 << (width - 1), 1 << width
+    if tag == "far:2Ge":
+        return None if item > 4 or half * item in (half, full) else half * item
+    return {"far:2G": half, "far:4G": full}[tag]
+
+
+def far_dims(t: Tensor) -> list[int]:
+    """the stride-carrying dimensions that ``rowpad`` / ``rowpad0`` vary: the innermost leading dimension with more than one
+    index, and the first one of a tensor of three or more dimensions"""
+    if t.numel() == 0 or t.dim() < 2:
+        return []
+    s, dims = tuple(t.shape), []
+    if t.numel() > s[-1]:
+        dims.append(max(d for d in range(t.dim() - 1) if s[d] > 1))
+    if t.dim() >= 3 and s[0] > 1 and 0 not in dims:
+        dims.append(0)
+    return dims
+
+
+def far_stride(n: int, item: int, boundary: int) -> int:
+    """elements: the smallest multiple of FAR_ALIGN that puts index n - 1 past ``boundary`` bytes"""
+    s = -(-(boundary // item + 1) // (n - 1))
+    return -(-s // FAR_ALIGN) * FAR_ALIGN
+
+
+def misreadings(i: int, stride: int, item: int, width: int) -> set[int]:
+    """byte offsets at which index ``i`` of the far dimension is looked for by code that forms the term in ``width`` bits at one
+    place: the element offset or the byte offset held in a signed or unsigned register, or the stride (in elements or bytes)
+    narrowed in front of a wide multiply.  The truth is among them."""
+    out = {i * stride * item}
+    for sg in (False, True):
+        out |= {wrap(i * stride, width, sg) * item, wrap(i * stride * item, width, sg), wrap(stride, width, sg) * i * item,
+                wrap(stride * item, width, sg) * i}
+    return out
+
+
+@dataclass
+class FarCase:
+    tag: str
+    dim: int
+    tensor: Tensor      # the view handed to the wrapper
+    strides: tuple
+    item: int
+    canon_numel: int
+    width: int
+
+    @property
+    def name(self) -> str:
+        return f"{self.tag}@{self.dim}"
+
+    def needs(self) -> tuple[int, int]:
+        """(bytes in front of the base, bytes from the base on) that the containment rule asks of the arena"""
+        shape, st, it, w = tuple(self.tensor.shape), self.strides, self.item, self.width
+        packed = self.canon_numel * it
+        others = sum((n - 1) * s for d, (n, s) in enumerate(zip(shape, st)) if d != self.dim) * it + it
+        last = (shape[self.dim] - 1) * st[self.dim]
+        # the stated rule: 2^(w-1) units below the base - elements where the element offset itself reaches 2^(w-1), bytes else
+        before = ((1 << (w - 1)) * (it if last >= 1 << (w - 1) else 1)) + packed
+        after = last * it + others + self.canon_numel * WIDEST
+        # and every enumerated misreading of every index, with what the other dimensions add to it
+        for i in range(shape[self.dim]):
+            for o in misreadings(i, st[self.dim], it, w):
+                before, after = max(before, -o), max(after, o + max(others, packed))
+        return before, after
+
+
+class Arena:
+    """one allocation for every far operand of a test module: ``nbytes`` of POISON32, views based in the middle"""
+
+    def __init__(self, nbytes: int, device, poisoned: bool = True) -> None:
+        assert nbytes % 512 == 0 and nbytes <= ARENA_CAP, nbytes
+        self.nbytes, self.base, self.poisoned = nbytes, nbytes // 2, poisoned
+        self.words = torch.empty(nbytes // 4, dtype=I32, device=device)
+        if poisoned:  # the CPU stage maps its arena lazily and touches the views only
+            self.words.fill_(POISON32)
+
+    @staticmethod
+    def bytes_for(width: int = 32, slack: int = 16 << 20) -> int:
+        """the largest need of any case: an f32 operand at 2^(width-1) elements, that distance on either side, plus slack"""
+        return 2 * ((1 << (width - 1)) * 4 + slack)
+
+    def view(self, shape, strides, dtype) -> Tensor:
+        item = torch.empty(0, dtype=dtype).element_size()
+        return self.words.view(dtype).as_strided(tuple(shape), tuple(strides), self.base // item)
+
+    def holds(self, case: FarCase) -> list[str]:
+        """the containment rule as pure arithmetic on base, strides and arena size: the gate in front of any run"""
+        before, after = case.needs()
+        bad = []
+        if before + after > ARENA_CAP:
+            bad.append(f"needs {before + after} bytes, more than the cap")
+        if before > self.base or after > self.nbytes - self.base:
+            bad.append(f"needs {before} bytes in front of the base and {after} behind it; the arena has {self.base} and {self.nbytes - self.base}")
+        return bad
+
+    def erase(self, view: Tensor) -> None:
+        """the view's elements back to poison"""
+        it = view.element_size()
+        assert it in (2, 4, 8), "a one-byte far operand would need the poison's phase"
+        as_int = {2: torch.int16, 4: I32, 8: I64}[it]
+        view.view(as_int).fill_({2: 0x7FC0, 4: POISON32, 8: POISON32 << 32 | POISON32}[it])
+
+    def dirty(self) -> int | None:
+        """byte offset of the first word that is not poison, None if there is none (one read of the arena, in pieces)"""
+        step = 1 << 28
+        counts = [torch.count_nonzero(self.words[a:a + step] != POISON32) for a in range(0, self.words.numel(), step)]
+        if not int(torch.stack(counts).sum()):
+            return None
+        k = next(i for i, c in enumerate(counts) if int(c))
+        return 4 * (k * step + int((self.words[k * step:(k + 1) * step] != POISON32).nonzero()[0]))
+
+
+def far_cases(t: Tensor, arena: Arena, width: int = 32) -> list[FarCase]:
+    """every far variant of the canonical operand ``t``: one stride-carrying dimension far, every other stride packed"""
+    assert t.is_contiguous()
+    out = []
+    for d in far_dims(t):
+        for tag in FAR_TAGS:
+            b = far_boundary(tag, t.element_size(), width)
+            if b is None:
+                continue
+            st = _packed(t.shape)
+            st[d] = far_stride(t.shape[d], t.element_size(), b)
+            assert (t.shape[d] - 1) * st[d] * t.element_size() > b and st[d] % FAR_ALIGN == 0
+            out.append(FarCase(tag, d, arena.view(t.shape, st, t.dtype), tuple(st), t.element_size(), t.numel(), width))
+    return out
+
+
+def applicable_far(t: Tensor, width: int = 32) -> set[tuple[str, int]]:
+    """the (tag, dimension) pairs ``far_cases`` must produce, from the layout table's own ``rowpad`` / ``rowpad0`` entries"""
+    tags, it, s = applicable_tags(t), t.element_size(), tuple(t.shape)
+    dims = set()
+    if "rowpad" in tags:
+        dims.add(max(d for d in range(t.dim() - 1) if s[d] > 1))
+    if "rowpad0" in tags:
+        dims.add(0)
+    dist = {}
+    for tag in FAR_TAGS:  # one tag per distinct byte distance
+        b = {"far:2G": 1 << (width - 1), "far:4G": 1 << width, "far:2Ge": (1 << (width - 1)) * it if it <= 4 else None}[tag]
+        if b is not None:
+            dist.setdefault(b, tag)
+    return {(tag, d) for tag in dist.values() for d in dims}
+
+
+def _far_row(rid: str, fn: str, build, only) -> Row:
+    return Row(rid, fn, lambda dev, seed=0: build(Gen(dev, SEED + 977 + seed)), (), tuple(only))
+
+
+# Rows of the far tests alone.  A stride passes 2^31 elements only where the far dimension has two indices (the last index lies
+# just past the boundary, so three rows put the stride at 2^30): these are the table's decode-step GEMMs at M = 2, whose
+# launchers hand their row strides to the kernels as int.
+FAR_ROWS: dict[str, Row] = {
+    "dec_linear:two_rows": _far_row("dec_linear:two_rows", "dec_linear", lambda g: dict(
+        x=g.f(2, 64), w=g.b(48, 64, scale=0.1), bias=g.f(48), ln=(g.f(64), g.f(64), EPS), act="gelu", resid=g.f(2, 48)), ("x", "resid")),
+    "dec_linear_ksplit:two_rows": _far_row("dec_linear_ksplit:two_rows", "dec_linear_ksplit", lambda g: dict(
+        x=g.f(2, 128), w=g.b(48, 128, scale=0.1), bias=g.f(48), k_split=2, act="gelu", resid=g.f(2, 48)), ("x", "resid")),
+    "dec_argmax:two_rows": _far_row("dec_argmax:two_rows", "dec_argmax", lambda g: dict(
+        x=g.f(2, 64), w=g.b(200, 64, scale=0.1), ln=(g.f(64), g.f(64), EPS)), ("x",)),
+}
+ALL_FAR_ROWS = {**ROWS, **FAR_ROWS}
+
+
+def check_row_far(ops, r: Row, dev, arena: Arena, compare: bool, hook=None, width: int = 32):
+    """check_row for the far variants: (problems, accepted triples, refused triples).  One operand is far per call, the others
+    compact.  A refusal leaves the in-place operands alone; an accepted call gives the canonical call's bits (a far ``out=`` /
+    in-place operand holds them in the view) and the arena outside the view stays poison."""
+    problems: list[str] = []
+    accepted, refused = [], []
+    kw0 = r.build(dev)
+    if hook:
+        hook.begin()
+    canon = snapshot(r, kw0, call(ops, r, kw0))
+    for path, t in operands(r.build(dev)):
+        if r.only is not None and path[0] not in r.only:
+            continue
+        for c in far_cases(t, arena, width):
+            where = f"{r.id} {path_name(path)} {c.name}"
+            gate = arena.holds(c)
+            if gate:  # never run what the arena cannot contain
+                problems += [f"{where}: {g}" for g in gate]
+                continue
+            c.tensor.copy_(t)
+            kw = replaced(r.build(dev), path, c.tensor)
+            before = snapshot(r, kw, None)
+            if hook:
+                hook.begin()
+            try:
+                res, exc = call(ops, r, kw), None
+            except REFUSALS as e:
+                if is_fault(e):
+                    raise GpuFault(f"{where}: {e}") from e
+                res, exc = None, e
+                if "pm_mi355x error 3" in str(e):
+                    problems.append(f"{where}: {e}")
+                    continue
+            except Exception as e:  # noqa: BLE001
+                problems.append(f"{where}: raised {type(e).__name__}: {e}")
+                continue
+            if hook:
+                problems += [f"{where}: {p}" for p in hook.end_far(r, path, c, kw, exc is not None)]
+            got = snapshot(r, kw, res)
+            if arena.poisoned:
+                arena.erase(c.tensor)
+                at = arena.dirty()
+                if at is not None:
+                    problems.append(f"{where}: {'refused but ' if exc else ''}wrote outside the view, first at byte {at - arena.base:+d} from its base")
+                    arena.words.fill_(POISON32)
+            if exc is not None:
+                refused.append((r.id, path_name(path), c.name))
+                changed = _diff(before, got)
+                if changed:
+                    problems.append(f"{where}: refused ({exc}) but wrote {changed}")
+                continue
+            accepted.append((r.id, path_name(path), c.name))
+            if compare:
+                bad = _diff(got, canon)
+                if bad:
+                    problems.append(f"{where}: accepted but {bad} differ from the compact call")
+    return problems, accepted, refused
