@@ -507,6 +507,29 @@ int pm_dec_sample_ragged(const float* logits, int64_t ldl, int64_t V, int64_t to
                          float* logprobs, const void* emb, const float* pos, const int32_t* key_start, float* x, int64_t d,
                          int32_t* ticket, int64_t B, void* stream);
 
+/* Repetition controls and eos bookkeeping of a decode step (csrc/controls.hip).
+ * pm_dec_controls: between the vocabulary projection and pm_dec_whisper_rules / the token tail.  logits (B, V) f32, row stride
+ *   ldl, edited in place; tokens int64 (B, Ttot); t = *pos_ptr, nothing happens while t + 1 < P.  The history of row b is
+ *   tokens[b, s .. t], s = key_start[b] (int32 (B,), clamped to 0..t) or 0 when key_start is NULL; ids outside [0, V) are skipped.
+ *     repetition_penalty r (finite, > 0; 1 = off): every DISTINCT id v of the history, once: l[v] = l[v] > 0 ? l[v] / r : l[v] * r,
+ *       one correctly rounded fp32 operation on the original value (-inf stays -inf, NaN stays NaN, a zero keeps its sign)
+ *     no_repeat_ngram n (0..8; 0 = off): with m ids of history and m >= n - 1, for every 0 <= i <= m - n whose ids i .. i + n - 2
+ *       equal the last n - 1 ids: l[h[i + n - 1]] = -inf (n = 1: every id of the history)
+ *     min_new_tokens (needs eos >= 0): while t + 1 - P < min_new_tokens, l[eos] = -inf.  eos = -1: none.
+ *   The result does not depend on thread scheduling.  PM_EINVAL before any launch: a null logits / tokens / pos_ptr, V <= 0 or
+ *   V > 262144 (the set of seen ids is V bits of LDS), ldl < V, r not finite or <= 0, n outside 0..8, min_new_tokens < 0 or
+ *   without eos, eos outside -1..V - 1.
+ * pm_dec_finish: behind the token tail (pm_dec_next_token, pm_dec_sample_topk, pm_dec_sample, ragged or not); t1 = *pos_ptr is the
+ *   position that tail wrote and advanced to; nothing happens while t1 < P.  finished int32 (B,), 0 = still running: a row with
+ *   finished[b] != 0 gets tokens[b, t1] = pad, tok_cur[b] = pad and (logprobs f32 (B, Ttot) or NULL) logprobs[b, t1] = 0;
+ *   otherwise a row whose tokens[b, t1] == eos records finished[b] = t1.  PM_EINVAL: a null tokens / tok_cur / finished /
+ *   pos_ptr, eos < 0, pad < 0. */
+int pm_dec_controls(float* logits, int64_t ldl, int64_t V, const int64_t* tokens, int64_t Ttot, const int32_t* pos_ptr, int64_t P,
+                    const int32_t* key_start, float repetition_penalty, int64_t no_repeat_ngram, int64_t min_new_tokens,
+                    int64_t eos, int64_t B, void* stream);
+int pm_dec_finish(int64_t* tokens, int64_t Ttot, int64_t* tok_cur, float* logprobs, int32_t* finished, const int32_t* pos_ptr,
+                  int64_t P, int64_t eos, int64_t pad, int64_t B, void* stream);
+
 /* ConvNeXt (reference: pytorch_models/image/convnext.py), csrc/convnext.hip.  NHWC rows, fp32 arithmetic; x_dtype / y_dtype
  * PM_BF16 or PM_F32; gamma / beta / bias f32.  The pointwise MLP and the downsample's Conv2d(C, 2C, 2, 2) run on the GEMMs above.
  *

@@ -68,6 +68,8 @@ SIGNATURES = {
     "pm_dec_sample_topk_ragged": ([_p, _l, _l, _l, ctypes.c_uint64, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _l, _p, _l, _p], c_int),
     "pm_dec_sample": ([_p, _l, _l, _l, _f, _f, ctypes.c_uint64, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _l, _p, _l, _p], c_int),
     "pm_dec_sample_ragged": ([_p, _l, _l, _l, _f, _f, ctypes.c_uint64, _p, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p], c_int),
+    "pm_dec_controls": ([_p, _l, _l, _p, _l, _p, _l, _p, _f, _l, _l, _l, _l, _p], c_int),
+    "pm_dec_finish": ([_p, _l, _p, _p, _p, _p, _l, _l, _l, _l, _p], c_int),
     "pm_layernorm": ([_p, _l, _i, _p, _p, _f, _p, _l, _i, _l, _l, _p], c_int),
     "pm_layernorm_ex": ([_p, _l, _i, _p, _p, _f, _i, _p, _l, _i, _p, _l, _i, _l, _l, _p], c_int),
     "pm_rmsnorm": ([_p, _l, _i, _p, _f, _p, _l, _i, _l, _l, _p], c_int),

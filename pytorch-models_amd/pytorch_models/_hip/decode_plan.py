@@ -170,6 +170,25 @@ def ragged_sample_args(logits: Tensor, topk: int, temperature: float, top_p: flo
     return (*a[:16], key_start.data_ptr(), *a[16:])
 
 
+def controls_args(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, key_start: Tensor | None, *, repetition_penalty: float = 1.0,
+                  no_repeat_ngram: int = 0, min_new_tokens: int = 0, eos: int | None = None) -> tuple:
+    """pm_dec_controls (csrc/controls.hip): the repetition penalty, the n-gram ban and the minimum length on the fp32 logits of the
+    row at *pos, in place; ``key_start`` (a ragged batch) keeps the padding out of the history, ``eos`` None = none"""
+    _unit_rows("controls_args", logits, tokens)
+    return (logits.data_ptr(), logits.stride(0), logits.shape[1], tokens.data_ptr(), tokens.shape[1], pos.data_ptr(), int(P),
+            ptr(key_start), float(repetition_penalty), int(no_repeat_ngram), int(min_new_tokens), -1 if eos is None else int(eos),
+            logits.shape[0], None)
+
+
+def finish_args(tokens: Tensor, tok_cur: Tensor, logprobs: Tensor | None, finished: Tensor, pos: Tensor, P: int, eos: int,
+                pad: int) -> tuple:
+    """pm_dec_finish (csrc/controls.hip), behind the token tail: ``finished`` int32 (rows,), 0 = still running; ``logprobs`` f32 like
+    ``tokens``, or None"""
+    _unit_rows("finish_args", tokens, logprobs)
+    return (tokens.data_ptr(), tokens.shape[1], tok_cur.data_ptr(), ptr(logprobs), finished.data_ptr(), pos.data_ptr(), int(P),
+            int(eos), int(pad), tokens.shape[0], None)
+
+
 def fused_args(x: Tensor, ln, w: Tensor, bias, kv: KV, out: Tensor, rows: int, heads: int, *, self_attn: bool, pos=None,
                n_keys: int) -> tuple:
     """pm_dec_attention_fused / _fused_kv32 / _fused_v2: LayerNorm + projection (+ cache append) + attention, self or cross"""

@@ -3,7 +3,8 @@
 New capability (the reference decodes nothing for Whisper: README.md:86).  Semantics = the reference's
 generic greedy loop (text/generator.py:23-35): at each step take argmax of the last position's logits and
 append it; here for a whole batch, with the self-attention K/V cached and the cross-attention K/V projected
-once.  The stop rule is build-defined (no tokenizer in the reference): a fixed number of new tokens.
+once.  The stop rule is build-defined (no tokenizer in the reference): a fixed number of new tokens, or - with ``eos_token_id`` -
+until every row has emitted its eos (pm_dec_finish keeps the rows' finished flags on the device).
 
 One step is ~8 launches per layer (csrc/decode.hip); the position and current tokens live on the device, so the
 step is captured ONCE into a HIP graph and replayed - no tracing compiler, no host round trips in the loop.
@@ -17,6 +18,7 @@ import torch
 from torch import Tensor
 
 from .._hip import DecLayer, decode_plan as plan, lib, ops
+from .._hip.controls import check_controls
 from .._hip.sampling import check_sampling, wants_sampling_tail
 from ..transformer import _f32
 
@@ -26,6 +28,10 @@ from ..transformer import _f32
 # kernel boundary (poll + barrier + sc1 round trips ~4-5 us against ~1.5 us + first loads), exactly what
 # cdna_hip_programming.md 5.6 reports for latency-bound phases.  The persistent path stays selectable and tested.
 PERSISTENT_BY_DEFAULT = False
+
+# With eos_token_id, GreedyDecoder.run reads the rows' finished flags back every POLL_EVERY steps (one synchronisation each) and
+# stops once every row has finished: T5Model.generate's figure (text/t5_generate.py)
+POLL_EVERY = 32
 
 
 def _ln(norm) -> tuple:
@@ -114,11 +120,13 @@ def _right_align(prompt: Tensor, lens: Tensor, width: int, pad: int) -> Tensor:
 
 class GreedyDecoder(plan.CapturedStep):
     """State + launch list of the decode step for one (decoder, batch, memory length) geometry."""
+    _own_eos = False  # BeamDecoder: ``eos`` is beam search's own argument, at any width
 
     def __init__(self, dec, memory: Tensor, prompt: Tensor, n_new: int, margins: bool = False, fused: bool = True,
                  topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False,
                  beams: int = 1, eos: int | None = None, prefill: bool = False, prefill_chunk: int | None = None, lengths=None,
-                 pad_token_id: int = 0, *, temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False) -> None:
+                 pad_token_id: int = 0, *, temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False,
+                 min_new_tokens: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0) -> None:
         """``kv32``: the reference-accuracy form of the same step - fp32 memory in, cross and self K/V kept in fp32 (nothing is
         rounded when it is cached; pm_dec_attention_fused_kv32), everything else as in the throughput path, whose projections
         are fp32-exact already (bf16 weights x activations split into three bf16 terms) - graph-replayed like it.
@@ -136,7 +144,24 @@ class GreedyDecoder(plan.CapturedStep):
         ``temperature`` / ``top_p`` / ``topk`` = 0 / ``return_logprobs``: the sampling tail (pm_dec_sample) in
         place of the token choice - taken only when temperature != 1, top_p != 1, topk == 0 or return_logprobs; with the defaults
         the launch list is the one it always was.  ``logprobs`` (B, Ttot) f32 then holds every stepped position's log-probability
-        (at temperature 1, after the rules); output_logprobs() returns the new positions in the caller's row layout."""
+        (at temperature 1, after the controls and the rules); output_logprobs() returns the new positions in the caller's row layout.
+        ``eos`` (beams = 1; under BeamDecoder it is beam search's own): row b FINISHES when a generated token equals it (a prompt-forced
+        token never does) - pm_dec_finish behind the token tail, whichever it is, keeps ``finished`` (B,) int32 (0 = running, else the
+        state column of the row's eos) and from then on writes ``pad_token_id`` and log-prob 0.0; run() polls
+        ``finished`` every POLL_EVERY steps and stops early (``steps_run``); output_lengths() counts the generated tokens.  No launch
+        in front of it changes: the ids up to each row's eos are those of the run without ``eos``.
+        ``min_new_tokens`` (needs ``eos``) / ``repetition_penalty`` / ``no_repeat_ngram_size``: one pm_dec_controls launch on the full
+        logits, between the vocabulary projection and the rules (whose -inf wins); any of them takes the full-logits route as
+        ``rules`` does (topk == 1 without sampling = pm_dec_sample_topk at k = 1, the arg-max).  A row's history is its real tokens,
+        prompt included, the padding of a ragged batch excluded.  With the defaults the launch list is the one it always was."""
+        E0 = dec.token_embs.weight
+        self._stops, self._controls = check_controls(
+            "greedy decode", None if self._own_eos else eos, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size, vocab=E0.shape[0], margins=margins,
+            beams=int(beams), path=path, kv32=kv32, fp32=E0.dtype == torch.float32)
+        self._eos = int(eos) if self._stops else None
+        self._ctl = dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram=int(no_repeat_ngram_size),
+                         min_new_tokens=int(min_new_tokens), eos=self._eos)
+        self.steps_run = 0
         self._sampling = check_sampling_tail("greedy decode", topk, temperature, top_p, return_logprobs, margins=margins, beams=int(beams),
                                              path=path, kv32=kv32, fp32=dec.token_embs.weight.dtype == torch.float32)
         if path not in ("auto", "launches", "persistent"):
@@ -169,6 +194,9 @@ class GreedyDecoder(plan.CapturedStep):
             raise ValueError("greedy decode: topk must be in 1..64")
         self.topk, self.temperature, self.top_p = topk, float(temperature), float(top_p)
         self._token_tail(dec, topk, seed, rules, margins, eos)
+        if self._stops:  # behind the tail, whichever it was: no launch in front of it changes
+            self.add(lib().pm_dec_finish, *plan.finish_args(self.tokens, self.tok_cur, self.logprobs, self.finished, self.pos, self.P,
+                                                            self._eos, self._pad))
         self._prefill_setup(dec)
 
     # ---- what is asked for
@@ -318,6 +346,7 @@ class GreedyDecoder(plan.CapturedStep):
         self.tokens[:, : self.P] = self.prompt
         self.margins = torch.zeros(B, self.Ttot, **f32) if margins else None
         self.logprobs = torch.zeros(B, self.Ttot, **f32) if self._sampling else None  # an attribute: the plan points into it
+        self.finished = torch.zeros(B, dtype=torch.int32, device=dev) if self._stops else None  # likewise; BeamDecoder has its own
         # d_model > 512: the final LayerNorm runs once as its own launch and the vocabulary projection without the
         # in-kernel LayerNorm, whose register budget would halve the feature tile (GPT-2 small: 101 -> ~55 us per step)
         self.split_final_norm = (d // 32 + 3) // 4 > 4
@@ -469,10 +498,12 @@ class GreedyDecoder(plan.CapturedStep):
         return self.xn, (None, None, eps)
 
     def _full_logits(self, xl: Tensor, ln: tuple, rules: "WhisperRules | None") -> None:
-        """logits of the last position for every row, then the logit filters (k = 1 after them = arg-max)"""
+        """logits of the last position for every row, then the controls and the logit filters (k = 1 after them = arg-max)"""
         B, V, P, L = self.B, self.V, self.P, lib()
         self.logits = torch.empty(B, V, dtype=torch.float32, device=xl.device)
         self.linear(xl, self._E, self.logits, ln=ln, mode=0)
+        if self._controls:  # in front of the rules: their -inf wins
+            self.add(L.pm_dec_controls, *plan.controls_args(self.logits, self.tokens, self.pos, P, self.key_start, **self._ctl))
         if rules is not None:
             i32 = dict(dtype=torch.int32, device=xl.device)
             sup, blk = torch.tensor(list(rules.suppress), **i32), torch.tensor(list(rules.blank), **i32)
@@ -494,7 +525,7 @@ class GreedyDecoder(plan.CapturedStep):
             if self._ragged:
                 return self.add(L.pm_dec_sample_ragged, *plan.ragged_sample_args(*state, self.key_start, self.x, self.ticket))
             return self.add(L.pm_dec_sample, *plan.sample_args(*state, self.x, self.ticket))
-        if topk == 1 and rules is None:
+        if topk == 1 and rules is None and not self._controls:
             self.linear(xl, E, None, ln=ln, mode=2)
             # token choice + the next step's embedding row + position advance: one launch
             if self._ragged:
@@ -639,11 +670,15 @@ class GreedyDecoder(plan.CapturedStep):
                 self._project_memory(mem2, wkv, bkv, out=kv)
         self.prompt.copy_(prompt if self.W == 1 else prompt.repeat_interleave(self.W, 0))
         self.tokens[:, : self.P] = self.prompt
+        if self._stops:
+            self.finished.zero_()
 
     def reset(self) -> None:
         self.pos.zero_()
         self.ticket.zero_()
         self.err.zero_()
+        if self._stops:
+            self.finished.zero_()  # no row has finished
         if self.path == "persistent":
             self.ps_cnt.zero_()  # arrival counters count up by epochs of the position: zero with it
         self.tok_cur.copy_(self.prompt[:, 0])
@@ -653,25 +688,61 @@ class GreedyDecoder(plan.CapturedStep):
         one_step = self.begin(graph)
         if self._pre_chunks:
             self.prefill()
-        for _ in range(self.n_steps):
-            one_step()
+        if not self._stops:
+            for _ in range(self.n_steps):
+                one_step()
+            self.steps_run = self.n_steps
+            return self.tokens
+        done = 0
+        while done < self.n_steps:
+            for _ in range(min(POLL_EVERY, self.n_steps - done)):
+                one_step()
+            done = min(done + POLL_EVERY, self.n_steps)
+            if done < self.n_steps and int(self.finished.min()) > 0:  # one read-back: every row has emitted its eos
+                break
+        self.steps_run = done
+        if done < self.n_steps:  # the positions never stepped: what pm_dec_finish would have written there
+            c0 = (self.P - 1 if self._pre_chunks else 0) + done + 1
+            self.tokens[:, c0:] = self._pad
+            for buf in (self.logprobs, self.margins):
+                if buf is not None:
+                    buf[:, c0:] = 0.0
         return self.tokens
+
+    def output_lengths(self) -> Tensor:
+        """(B,) int64: the number of generated tokens of every row of the last run, its eos included; n_new for a row that never
+        finished (and for every row of a decoder built without ``eos``).  The caller's row order, ragged or not."""
+        n = self.Ttot - self.P
+        if not self._stops:
+            return torch.full((self.B,), n, dtype=torch.int64, device=self.tokens.device)
+        f = self.finished.to(torch.int64)
+        return torch.where(f > 0, f - self.P + 1, torch.full_like(f, n))
+
+    def _live_margins(self) -> "Tensor | None":
+        """margins with zeros behind a finished row's eos: the default tail goes on writing the margins of what it picks there"""
+        if self.margins is None or not self._stops:
+            return self.margins
+        f = self.finished.to(torch.int64)[:, None]
+        cols = torch.arange(self.Ttot, device=self.margins.device)[None, :]
+        return torch.where((f > 0) & (cols > f), torch.zeros((), device=self.margins.device), self.margins)
 
     def output(self) -> tuple:
         """(tokens, margins or None) of the last run in the caller's layout.  Rectangular prompts: the state itself.  Ragged: (B,
         P + n_new), row b = its prompt, its new ids, then P - len_b times pad_token_id (margins: zeros) - host indexing of the
         right-aligned state."""
+        margins = self._live_margins()
         if not self._ragged:
-            return self.tokens, self.margins
+            return self.tokens, margins
         dev = self.tokens.device
         idx = torch.arange(self._P_in + self.Ttot - self.P)[None, :] + self._starts[:, None]
         live, idx = (idx < self.Ttot).to(dev), idx.clamp(max=self.Ttot - 1).to(dev)
         toks = torch.where(live, self.tokens.gather(1, idx), torch.full((), self._pad, dtype=torch.int64, device=dev))
-        marg = None if self.margins is None else torch.where(live, self.margins.gather(1, idx), torch.zeros((), device=dev))
+        marg = None if margins is None else torch.where(live, margins.gather(1, idx), torch.zeros((), device=dev))
         return toks, marg
 
     def output_logprobs(self) -> Tensor:
-        """(B, n_new) f32: the log-probability of every new token of the last run (at temperature 1, after the rules), in the caller's
+        """(B, n_new) f32: the log-probability of every new token of the last run (at temperature 1, of the logits after the controls
+        and the rules; exactly 0.0 behind a finished row's eos, so sum(-1) is the sequence log-probability), in the caller's
         row order - for a ragged run row b's new ids sit at state columns P .. Ttot - 1 whatever its length, as output() knows"""
         if self.logprobs is None:
             raise ValueError("greedy decode: this decoder was built without return_logprobs / the sampling tail")
@@ -693,6 +764,7 @@ class BeamDecoder(GreedyDecoder):
     ``logits`` (B * W, V) f32 of the last step (after the rules), ``self_k`` / ``self_v`` per layer (B * W, H, P + n, 64).
     ``prefill``: GreedyDecoder's prompt pass at all B * W rows - the W rows of a clip hold the same prompt, so their caches come
     out identical up to position P - 2, which is what the beam kernels assume at the first generated position."""
+    _own_eos = True
 
     def __init__(self, dec, memory: Tensor | None, prompt: Tensor, n_new: int, beams: int, *, eos: int | None = None,
                  rules: "WhisperRules | None" = None, path: str = "auto", kv32: bool = False, fused: bool = True,
@@ -790,7 +862,8 @@ def beam_decode(dec, memory: Tensor | None, prompt: Tensor, n_new: int, *, beams
 def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: bool = True, margins: bool = False,
                   fused: bool = True, topk: int = 1, seed: int = 0, rules: "WhisperRules | None" = None, path: str = "auto",
                   kv32: bool = False, prefill: bool = False, prefill_chunk: int | None = None, lengths=None, pad_token_id: int = 0,
-                  temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False):
+                  temperature: float = 1.0, top_p: float = 1.0, return_logprobs: bool = False, eos_token_id: int | None = None,
+                  return_lengths: bool = False, min_new_tokens: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
     """tokens (B, P + n_new) int64 [and per-position diagnostic margins].  fused=False uses the unfused
     projection + attention launches (same arithmetic, 2 more launches per layer); topk > 1 samples each token from the
     softmax over the k largest logits on the device (same seed -> same ids); path: "persistent" (all layers of a step in
@@ -808,16 +881,36 @@ def greedy_decode(dec, memory: Tensor, prompt: Tensor, n_new: int, *, graph: boo
     cut to the smallest set of highest logits whose mass reaches top_p (ties at the boundary kept), one draw keyed by (seed, cache
     position, row).  With ``return_logprobs`` the result is (tokens, logprobs (B, n_new) f32): each new token's log-probability at
     temperature 1 after the rules, what score() returns for it.  Works with prefill, lengths and rules; not with margins, beams
-    (ValueError), path="persistent", kv32 or fp32 parameters (NotImplementedError).  With the defaults nothing changes."""
-    st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32, prefill=prefill,
+    (ValueError), path="persistent", kv32 or fp32 parameters (NotImplementedError).  With the defaults nothing changes.
+    ``eos_token_id`` (None = never finish, also under ``rules``): row b finishes when a GENERATED token equals it (a prompt-forced one
+    never does).  Its eos and the eos's log-prob stay; every later position holds ``pad_token_id`` (default 0) and log-prob exactly
+    0.0, so logprobs.sum(-1) is the sequence log-probability and logprobs.sum(-1) / n_new Whisper's avg_logprob, eos included.  The
+    run ends once every row has finished (polled every POLL_EVERY steps); the ids up to each row's eos are those of the run without
+    it.  ``return_lengths`` appends n_new (B,) int64 as the LAST element of the result: the generated tokens of the row, its eos
+    included, n_new for a row that never finished.
+    ``min_new_tokens`` (needs eos_token_id): the logit of eos_token_id is -inf while fewer tokens have been generated.
+    ``repetition_penalty`` r (finite, > 0): every distinct id v of the row's history, once: l[v] / r if l[v] > 0 else l[v] * r.
+    ``no_repeat_ngram_size`` n (0..8): no n-gram occurs twice in a row - every id that would complete an n-gram the history (prompt
+    included) already holds gets -inf; n = 1 bans every id of the history.  History = the row's real tokens (the padding of a
+    ragged batch excluded); order in the step: vocabulary projection, these controls, the rules (whose -inf wins), the token tail;
+    a reported log-prob is of the logits after controls and rules.  Any of the three takes the full-logits route as ``rules`` does.
+    All of this works with prefill, lengths, rules, top-k and the sampling tail; ``eos_token_id`` alone also with margins (zeros behind
+    the eos).  Refused before anything touches a device: a logit control with margins, beams (ValueError), path="persistent", kv32
+    or fp32 parameters (NotImplementedError), eos / pad outside the vocabulary (ValueError)."""
+    check_controls("greedy decode", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size, return_lengths,
+                   vocab=dec.token_embs.weight.shape[0], margins=margins, path=path, kv32=kv32,
+                   fp32=dec.token_embs.weight.dtype == torch.float32)
+    st = GreedyDecoder(dec, memory, prompt, n_new, margins, fused, topk, seed, rules, path, kv32, eos=eos_token_id, prefill=prefill,
                        prefill_chunk=prefill_chunk, lengths=lengths, pad_token_id=pad_token_id, temperature=temperature, top_p=top_p,
-                       return_logprobs=return_logprobs)
+                       return_logprobs=return_logprobs, min_new_tokens=min_new_tokens, repetition_penalty=repetition_penalty,
+                       no_repeat_ngram_size=no_repeat_ngram_size)
     st.run(graph)
     st.check()
     toks, marg = st.output()
-    if return_logprobs:
-        return toks, st.output_logprobs()
-    return (toks, marg) if margins else toks
+    res = (toks, st.output_logprobs()) if return_logprobs else (toks, marg) if margins else (toks,)
+    if return_lengths:
+        res += (st.output_lengths(),)
+    return res if len(res) > 1 else res[0]
 
 
 @torch.no_grad()

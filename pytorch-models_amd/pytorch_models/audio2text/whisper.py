@@ -165,7 +165,8 @@ class WhisperDecoder(nn.Module):
     def generate(self, memory: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
                  prefill: bool = False, lengths=None, pad_token_id: int = 0, topk: int = 1, seed: int = 0, temperature: float = 1.0,
-                 top_p: float = 1.0, return_logprobs: bool = False):
+                 top_p: float = 1.0, return_logprobs: bool = False, return_lengths: bool = False, min_new_tokens: int = 0,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """Batched greedy decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids.  ``rules``: a
         generate.WhisperRules (token suppression, timestamp pairing / monotonicity) applied to the logits on the device;
         ``path``: "persistent" / "launches" / "auto" (generate.GreedyDecoder).  ``beams`` > 1: beam search of that width
@@ -176,12 +177,20 @@ class WhisperDecoder(nn.Module):
         new ids, then P - len_b times ``pad_token_id``: what generate() returns for that clip and prompt alone (generate.greedy_decode;
         bf16 model and memory, beams = 1, not path="persistent").
         ``topk`` (1..64; 0 = the whole vocabulary), ``seed``, ``temperature`` (0 = arg-max), ``top_p``, ``return_logprobs`` (-> (ids,
-        logprobs (B, max_new_tokens) f32), each new token's log-probability at temperature 1 after the rules - the mean over a
-        transcript is Whisper's avg_logprob): generate.greedy_decode's sampling; bf16 model and memory, beams = 1, not
-        path="persistent"."""
+        logprobs (B, max_new_tokens) f32), each new token's log-probability at temperature 1 after the controls and the rules; with
+        ``eos_token_id`` logprobs.sum(-1) / n_new is Whisper's avg_logprob): generate.greedy_decode's sampling; bf16 model and memory,
+        beams = 1, not path="persistent".
+        ``eos_token_id`` (beams = 1; None = never finish, also under ``rules``): a row finishes at its first GENERATED eos, later positions hold ``pad_token_id`` and log-prob 0.0,
+        the run ends once every row has finished; ``return_lengths`` appends n_new (B,) int64 (eos included) as the last element of the
+        result; ``min_new_tokens`` / ``repetition_penalty`` / ``no_repeat_ngram_size`` (0..8): the logit controls of
+        generate.greedy_decode (one pm_dec_controls launch per step); bf16 parameters, beams = 1, not path="persistent"."""
+        from .._hip.controls import check_controls
         from .generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
 
         fp32 = self.token_embs.weight.dtype == torch.float32
+        check_controls("WhisperDecoder.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size,
+                       return_lengths, vocab=self.token_embs.weight.shape[0], beams=1 if beams == 1 and not return_beams else max(beams, 2),
+                       path=path, kv32=memory is not None and memory.dtype == torch.float32, fp32=fp32)
         check_sampling_tail("WhisperDecoder.generate", topk, temperature, top_p, return_logprobs,
                             beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
                             kv32=memory is not None and memory.dtype == torch.float32, fp32=fp32)
@@ -207,7 +216,8 @@ class WhisperDecoder(nn.Module):
             return greedy_exact(self, memory, prompt, max_new_tokens)
         return greedy_decode(self, memory, prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
                              lengths=lengths, pad_token_id=pad_token_id, topk=topk, seed=seed, temperature=temperature, top_p=top_p,
-                             return_logprobs=return_logprobs)
+                             return_logprobs=return_logprobs, eos_token_id=eos_token_id, return_lengths=return_lengths, min_new_tokens=min_new_tokens,
+                             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
 
 class Whisper(nn.Module):
@@ -242,7 +252,8 @@ class Whisper(nn.Module):
     def generate(self, x: Tensor, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, rules=None, path: str = "auto",
                  exact: bool = False, beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
                  prefill: bool = False, lengths=None, pad_token_id: int = 0, topk: int = 1, seed: int = 0, temperature: float = 1.0,
-                 top_p: float = 1.0, return_logprobs: bool = False):
+                 top_p: float = 1.0, return_logprobs: bool = False, return_lengths: bool = False, min_new_tokens: int = 0,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """log-mel (B, n_mels, T) + prompt ids (B, P) -> greedy ids (B, P + max_new_tokens); ``beams`` > 1: beam search
         (WhisperDecoder.generate), with ``exact=True`` on the fp32-cache step (B * beams * n_heads <= 256).
         ``exact=True`` (bf16 model): the whole pipeline - encoder, cross K/V, decoder, caches - in fp32 on an fp32 copy of
@@ -251,9 +262,16 @@ class Whisper(nn.Module):
         parameters are fp32 always decodes this way.  ``prefill``: WhisperDecoder.generate's; not with ``exact``.
         ``lengths`` / ``pad_token_id``: WhisperDecoder.generate's ragged prompt batch; not with ``exact``, beams or fp32 parameters.
         ``topk`` / ``seed`` / ``temperature`` / ``top_p`` / ``return_logprobs``: WhisperDecoder.generate's sampling; not with ``exact``,
-        beams or fp32 parameters."""
+        beams or fp32 parameters.
+        ``eos_token_id`` (beams = 1) / ``return_lengths`` / ``min_new_tokens`` / ``repetition_penalty`` / ``no_repeat_ngram_size``:
+        WhisperDecoder.generate's eos stopping and logit controls; not with ``exact``, beams or fp32 parameters."""
+        from .._hip.controls import check_controls
         from .generate import check_ragged, check_sampling_tail
 
+        check_controls("Whisper.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size,
+                       return_lengths, vocab=self.decoder.token_embs.weight.shape[0],
+                       beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
+                       fp32=self.decoder.token_embs.weight.dtype == torch.float32)
         check_sampling_tail("Whisper.generate", topk, temperature, top_p, return_logprobs,
                             beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
                             fp32=self.decoder.token_embs.weight.dtype == torch.float32)
@@ -286,7 +304,8 @@ class Whisper(nn.Module):
             return twin.generate(x, prompt, max_new_tokens)
         return self.decoder.generate(self.encoder(x), prompt, max_new_tokens, graph=graph, rules=rules, path=path, prefill=prefill,
                                      lengths=lengths, pad_token_id=pad_token_id, topk=topk, seed=seed, temperature=temperature,
-                                     top_p=top_p, return_logprobs=return_logprobs)
+                                     top_p=top_p, return_logprobs=return_logprobs, eos_token_id=eos_token_id, return_lengths=return_lengths, min_new_tokens=min_new_tokens,
+                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     def exact_copy(self) -> "Whisper":
         """fp32 twin of this model (same values: bf16 -> fp32 is exact), rebuilt when a parameter changes."""

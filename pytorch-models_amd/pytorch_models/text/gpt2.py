@@ -125,7 +125,8 @@ class GPT2(nn.Module):
     def generate(self, prompt: Tensor, max_new_tokens: int, *, graph: bool = True, topk: int = 1, seed: int = 0,
                  path: str = "auto", beams: int = 1, eos_token_id: int | None = None, return_beams: bool = False,
                  prefill: bool = False, lengths=None, pad_token_id: int = 0, temperature: float = 1.0, top_p: float = 1.0,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, return_lengths: bool = False, min_new_tokens: int = 0,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """Batched decoding with a KV cache: (B, P) int64 prompt -> (B, P + max_new_tokens) ids; greedy (topk = 1) or
         top-k sampling on the device (softmax over the k largest logits; the same seed gives the same ids); ``beams`` > 1:
         beam search (audio2text.generate.beam_decode), with ``return_beams`` (tokens (B, beams, P + n), scores (B, beams)).
@@ -134,8 +135,17 @@ class GPT2(nn.Module):
         new ids, then P - len_b times ``pad_token_id``: what generate() returns for that row alone (greedy; top-k draws are keyed
         by the cache position, so they differ from the row's own run).  bf16 parameters, beams = 1, not path="persistent".
         ``temperature`` (0 = arg-max), ``top_p``, ``topk`` = 0 (the whole vocabulary), ``return_logprobs`` (-> (ids, logprobs (B,
-        max_new_tokens) f32)): the sampling tail of generate.greedy_decode; bf16 parameters, beams = 1, not path="persistent"."""
+        max_new_tokens) f32)): the sampling tail of generate.greedy_decode; bf16 parameters, beams = 1, not path="persistent".
+        ``eos_token_id`` (beams = 1): a row finishes at its first GENERATED eos, later positions hold ``pad_token_id`` and log-prob 0.0,
+        the run ends once every row has finished; ``return_lengths`` appends n_new (B,) int64 (eos included) as the last element of the
+        result; ``min_new_tokens`` / ``repetition_penalty`` / ``no_repeat_ngram_size`` (0..8): the logit controls of
+        generate.greedy_decode (one pm_dec_controls launch per step); bf16 parameters, beams = 1, not path="persistent"."""
+        from .._hip.controls import check_controls
         from ..audio2text.generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
+
+        check_controls("GPT2.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size, return_lengths,
+                       vocab=self.token_embs.weight.shape[0], beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
+                       fp32=self.token_embs.weight.dtype == torch.float32)
 
         check_sampling_tail("GPT2.generate", topk, temperature, top_p, return_logprobs, beams=1 if beams == 1 and not return_beams else max(beams, 2),
                             path=path, fp32=self.token_embs.weight.dtype == torch.float32)
@@ -155,7 +165,8 @@ class GPT2(nn.Module):
             return greedy_exact(self, None, prompt, max_new_tokens)
         return greedy_decode(self, None, prompt, max_new_tokens, graph=graph, topk=topk, seed=seed, path=path, prefill=prefill,
                              lengths=lengths, pad_token_id=pad_token_id, temperature=temperature, top_p=top_p,
-                             return_logprobs=return_logprobs)
+                             return_logprobs=return_logprobs, eos_token_id=eos_token_id, return_lengths=return_lengths, min_new_tokens=min_new_tokens,
+                             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     @staticmethod
     def from_hf(model_tag: str, *, pretrained=False, **kwargs) -> "GPT2":

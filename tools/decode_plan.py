@@ -188,6 +188,10 @@ CASES = {
     "whisper_sample": _greedy(topk=0, temperature=0.7, top_p=0.9, return_logprobs=True, rules=True),  # pm_dec_sample: the log-prob buffer
     "whisper_logprobs": _greedy(return_logprobs=True),  # the arg-max of the defaults through the sampling tail
     "whisper_rules": _greedy(rules=True),
+    "whisper_eos": _greedy(eos=200, margins=True),  # pm_dec_finish behind the default tail: the finished flags
+    "whisper_controls": _greedy(rules=True, eos=200, min_new_tokens=2, repetition_penalty=1.3, no_repeat_ngram_size=2,
+                                return_logprobs=True),  # pm_dec_controls in front of the rules, pm_dec_finish with the log-prob buffer
+    "gpt2_ragged_controls": _greedy(model=dict(cross=False), lengths=(2, 1, 2), eos=5, no_repeat_ngram_size=2),  # key_start in the controls
     "whisper_margins": _greedy(margins=True),
     "whisper_mlp256": _greedy(model=dict(hid=256)),  # no K-split anywhere
     "gpt2_d128": _greedy(model=dict(cross=False)),
