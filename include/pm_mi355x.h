@@ -14,7 +14,9 @@
  *  - leading dimensions (ld*) are in ELEMENTS of the tensor's dtype;
  *  - return value: 0 = OK, otherwise a PM_E* code (pm_strerror gives text).  Arguments are
  *    validated on the host before any launch; a rejected call launches nothing;
- *  - dtypes: PM_BF16 / PM_F32 below.
+ *  - dtypes: PM_BF16 / PM_F32 below;
+ *  - data pointers must be non-null even when an extent is 0 (the null check comes first and returns PM_EINVAL); the wrappers of
+ *    pytorch_models/_hip/ops.py never call the library with an empty operand: they return the empty result themselves.
  */
 #ifndef PM_MI355X_H
 #define PM_MI355X_H
@@ -76,7 +78,8 @@ int64_t pm_linear_ws_bytes(void);
 
 /* Host-only query: the kernel a pm_linear_bf16_ws call with these arguments would launch.  1 = 128 x 128, 2 = persistent
  * 256 x 128, 3 = 256 x 256, 4 / 5 = the stream-K / hybrid experiments, 6 / 7 = (64 MI) x 256 tiles of 256 / 320 rows; 0 when
- * M == 0 (nothing is launched); minus the error code the call would return.  The launch takes its decision from the same
+ * M == 0 with non-null pointers (nothing is launched; an empty tensor's null pointer is PM_EINVAL like any other, so ops.linear_plan
+ * answers 0 for an empty batch itself and does not ask); minus the error code the call would return.  The launch takes its decision from the same
  * function.  Pointers are looked at for null and alignment only: nothing is dereferenced or launched, no GPU is needed.
  * PM_GEMM_KERNEL (read once per process) forces a kernel where it applies and silently falls through where it does not -
  * this query is how a test learns which one ran. */

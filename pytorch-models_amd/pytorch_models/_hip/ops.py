@@ -83,6 +83,35 @@ def _need(cond: bool, msg: str) -> None:
         raise ValueError(msg)
 
 
+def _empty(who: str, count: int, *inner: int) -> bool:
+    """The empty-batch contract, called once everything is validated and in front of the launch.  ``count``:
+    the number of independent rows or problems of the call (a product where there are several); ``inner``: every extent a result
+    element is reduced over or laid out by, and the size of one sample.  True for an empty batch - the caller returns its (empty)
+    result and the library is not called: data_ptr() of a tensor without elements is null, which every C entry point refuses -,
+    ValueError for an empty inner or sample extent, False (the hot path: two comparisons) otherwise."""
+    if count > 0 and 0 not in inner:
+        return False
+    _need(0 not in inner and count == 0,
+          f"{who}: an extent other than the batch is 0 (batch {count}, the others {inner}): only the batch may be empty")
+    return True
+
+
+def _rows(who: str, rows: int, *inner: int) -> None:
+    """The decode-step family's side of the empty-batch contract: its state (caches, tickets, the K-split workspace) is allocated
+    per batch by the launch plan and the C entry points refuse rows <= 0, so an empty batch is refused here, by name."""
+    _need(rows > 0 and 0 not in inner,
+          f"{who}: an empty batch or extent is refused (rows {rows}, the others {inner}): a decode step's state is allocated per batch")
+
+
+def refuse_empty_batch(who: str, *ts) -> None:
+    """A model entry point's side of the empty-batch contract where it refuses: ValueError naming the entry point and the empty batch,
+    in front of any wrapper call."""
+    for t in ts:
+        if isinstance(t, Tensor) and t.dim() >= 1 and t.shape[0] == 0:
+            raise ValueError(f"{who}: an empty batch is refused (an operand of shape {tuple(t.shape)}): the caches and the launch plan "
+                             "of a decoder are allocated per batch")
+
+
 def capturing() -> bool:
     """The current stream is being captured into a HIP graph.  False wherever no HIP context exists (a process that has not
     touched the GPU cannot be capturing), so the host-only helpers below stay usable without one."""
@@ -127,6 +156,8 @@ def ln_stats_finalize(partials: Tensor, N: int, eps: float) -> Tensor:
           and partials.shape[1:] == (N // 64, 2), "ln_stats_finalize: partials must be contiguous f32 (M, N / 64, 2)")
     M = partials.shape[0]
     stats = torch.empty((M, 2), dtype=torch.float32, device=partials.device)
+    if _empty("ln_stats_finalize", M, N):
+        return stats
     rc = _launch("ln_stats_finalize", float(partials.numel() * 4), lambda: lib().pm_ln_stats_finalize(
         partials.data_ptr(), stats.data_ptr(), M, N, float(eps), _stream()))
     check(rc, "pm_ln_stats_finalize")
@@ -179,6 +210,8 @@ def linear(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "none
     _cuda(x, w, bias, resid, out, ln_stats, ln_s)
     args, out, rows = _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period)
     M, N, K = args[14:17]
+    if _empty("linear", M, N, K):
+        return (out, rows) if want_row_stats else out
     rc = _launch("linear_bf16", (2.0 * M * N * K, _linear_bytes(x, w, out, resid)), lambda: lib().pm_linear_bf16_ws(*args, _stream()))
     check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
     return (out, rows) if want_row_stats else out
@@ -222,9 +255,13 @@ def linear_plan(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = 
                 out_dtype: torch.dtype = torch.bfloat16, out: Tensor | None = None, ln_stats: Tensor | None = None,
                 ln_s: Tensor | None = None, want_row_stats: bool = False, resid_period: int = 0) -> int:
     """pm_linear_bf16_plan: the kernel id (1 .. 7) linear() would launch with these operands - the arguments are built by the
-    same function -, 0 for M == 0, or minus the error code.  Host arithmetic only: nothing is launched and the tensors may live
-    on the CPU (pointers are looked at for null and alignment).  PM_GEMM_KERNEL is read once per process."""
+    same function -, 0 for M == 0 (linear() then returns its empty result without a launch, and the library is not asked: an empty
+    operand's pointer is null, which the C query refuses as it refuses any null pointer), or minus the error code; N == 0 or K == 0
+    raise as they do in linear().  Host arithmetic only: nothing is launched and the tensors may live on the CPU (pointers are looked
+    at for null and alignment).  PM_GEMM_KERNEL is read once per process."""
     args, _, _ = _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_row_stats, resid_period)
+    if _empty("linear_plan", *args[14:17]):
+        return 0
     return int(lib().pm_linear_bf16_plan(*args))
 
 
@@ -252,6 +289,8 @@ def linear_f32(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("linear_f32: rows of out overlap")
     _need(out.dtype == torch.float32 and out.shape == (M, N) and out.stride(1) == 1, "linear_f32: bad out")
+    if _empty("linear_f32", M, N, K):
+        return out
     rc = _launch("linear_f32", 2.0 * M * N * K, lambda: lib().pm_linear_f32(
         x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0), bias.data_ptr() if bias is not None else None,
         resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0, resid_period, out.data_ptr(),
@@ -267,7 +306,7 @@ def attention_f32(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = 
     _need(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention_f32: operands must be (B, L, H*hd)")
     B, Lq, D = q.shape
     Lk = k.shape[1]
-    _need(D % n_heads == 0 and k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention_f32: shape mismatch")
+    _need(n_heads > 0 and D % n_heads == 0 and k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention_f32: shape mismatch")
     for t in (q, k, v):
         _need(t.dtype == torch.float32 and t.stride(2) == 1, "attention_f32: f32 operands with unit last stride")
     out = torch.empty((B, Lq, D), dtype=torch.float32, device=q.device)
@@ -278,6 +317,8 @@ def attention_f32(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = 
         sb = 0 if bias.shape[0] == 1 else bias.stride(0)
         sh = 0 if bias.shape[1] == 1 else bias.stride(1)
         sq = bias.stride(2)
+    if _empty("attention_f32", B * Lq, Lk, D):
+        return out
     rc = _launch("attention_f32", 4.0 * B * n_heads * Lq * Lk * (D // n_heads), lambda: lib().pm_attention_generic_f32(
         q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
         out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, D // n_heads, int(causal),
@@ -304,6 +345,8 @@ def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, 
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("layernorm: rows of out overlap")
     _need(out.shape == (M, d) and out.stride(1) == 1, "layernorm: out must be (M, d), row-major")
+    if _empty("layernorm", M, d):
+        return out
     gp, bp = (gamma.data_ptr(), beta.data_ptr()) if gamma is not None else (None, None)
     nbytes = float(M * d * (x.element_size() + out.element_size() + (resid.element_size() if resid is not None else 0)))
     if act == "none" and resid is None and gamma is not None:
@@ -325,6 +368,8 @@ def rmsnorm(x: Tensor, gamma: Tensor, eps: float, out_dtype: torch.dtype | None 
     M, d = x.shape
     _need(gamma.dtype == torch.float32 and gamma.numel() == d and gamma.is_contiguous(), "rmsnorm: gamma must be contiguous f32 (d)")
     out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
+    if _empty("rmsnorm", M, d):
+        return out
     rc = _launch("layernorm", float(M * d * (x.element_size() + out.element_size())), lambda: lib().pm_rmsnorm(
         x.data_ptr(), x.stride(0), _dt(x), gamma.data_ptr(), float(eps), out.data_ptr(), out.stride(0), _dt(out), M, d, _stream()))
     check(rc, f"pm_rmsnorm(M={M}, d={d})")
@@ -337,6 +382,8 @@ def geglu(h: Tensor) -> Tensor:
     _need(h.dim() == 2 and h.dtype == torch.bfloat16 and h.stride(1) == 1 and h.shape[1] % 2 == 0, "geglu: bf16 (M, 2F) rows")
     M, F = h.shape[0], h.shape[1] // 2
     out = torch.empty((M, F), dtype=torch.bfloat16, device=h.device)
+    if _empty("geglu", M, F):
+        return out
     rc = _launch("geglu", float(M * F * 6), lambda: lib().pm_geglu(h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0), M, F, _stream()))
     check(rc, f"pm_geglu(M={M}, F={F})")
     return out
@@ -353,7 +400,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
     _need(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "attention: operands must be (B, L, H*hd)")
     B, Lq, D = q.shape
     Lk = k.shape[1]
-    _need(D % n_heads == 0 and k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention: shape mismatch")
+    _need(n_heads > 0 and D % n_heads == 0 and k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention: shape mismatch")
     hd = D // n_heads
     for t in (q, k, v):
         _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention: bf16 operands with unit last stride")
@@ -365,12 +412,15 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
     args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
             v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, int(causal))
     sb = sh = sq = 0
+    empty = _empty("attention", B * Lq, Lk, D)
     if bias is not None:
         _need(bias.dim() == 4 and bias.dtype == torch.float32 and bias.shape[2:] == (Lq, Lk) and bias.stride(3) == 1
               and bias.shape[0] in (1, B) and bias.shape[1] in (1, n_heads), "attention: bias must be f32 (1|B, 1|H, Lq, Lk)")
         sb = 0 if bias.shape[0] == 1 else bias.stride(0)
         sh = 0 if bias.shape[1] == 1 else bias.stride(1)
         sq = bias.stride(2)
+    if empty:
+        return out
     if hd != 64:
         rc = _launch("attention_generic", 4.0 * B * n_heads * Lq * Lk * hd, lambda: lib().pm_attention_generic_bf16(
             *args[:16], hd, int(causal), bias.data_ptr() if bias is not None else None, sb, sh, sq, _stream()))
@@ -392,12 +442,15 @@ def conv2d_nhwc(x: Tensor, w: Tensor, bias: Tensor | None, stride: int = 1, pad:
     _need(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "conv2d_nhwc: bf16 operands")
     N, H, W, Cin = x.shape
     Cout, kh, kw, cg = w.shape
-    _need(Cin % groups == 0 and Cout % groups == 0 and cg == Cin // groups, "conv2d_nhwc: channel / group mismatch")
+    _need(groups > 0 and stride > 0 and Cin % groups == 0 and Cout % groups == 0 and cg == Cin // groups, "conv2d_nhwc: channel / group mismatch")
+    empty = _empty("conv2d_nhwc", N, H, W, Cin, Cout, kh, kw)
     _need(bias is None or (bias.dtype == torch.float32 and bias.numel() == Cout and bias.is_contiguous()),
           "conv2d_nhwc: bias must be contiguous f32 (Cout)")
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
     _need(resid is None or (resid.shape == out.shape and resid.dtype == torch.bfloat16 and resid.is_contiguous()), "conv2d_nhwc: resid must match the output")
+    if empty:
+        return out
     rc = _launch("conv2d_nhwc", 2.0 * N * Ho * Wo * Cout * kh * kw * cg, lambda: lib().pm_conv2d_nhwc_bf16(
         x.data_ptr(), N, H, W, Cin, w.data_ptr(), bias.data_ptr() if bias is not None else None,
         resid.data_ptr() if resid is not None else None, out.data_ptr(), Cout, kh, kw, stride, pad, groups, ACT[act], _stream()))
@@ -411,6 +464,8 @@ def mean_rows(x: Tensor) -> Tensor:
     _need(x.dim() == 3 and x.is_contiguous() and x.dtype == torch.bfloat16, "mean_rows: contiguous bf16 (N, R, C)")
     N, R, C = x.shape
     out = torch.empty((N, C), dtype=torch.bfloat16, device=x.device)
+    if _empty("mean_rows", N, R, C):
+        return out
     rc = _launch("mean_rows", 1.0 * N * R * C, lambda: lib().pm_mean_rows_bf16(x.data_ptr(), out.data_ptr(), N, R, C, _stream()))
     check(rc, f"pm_mean_rows_bf16(N={N}, R={R}, C={C})")
     return out
@@ -423,6 +478,7 @@ def vit_tokens(imgs: Tensor, w2d: Tensor, bias: Tensor, pe: Tensor, cls: Tensor 
           "vit_tokens: imgs must be contiguous f32 (N, 3, H, W)")
     N, _, H, W = imgs.shape
     d = w2d.shape[0]
+    _need(patch > 0, "vit_tokens: the patch size must be positive")
     L = (H // patch) * (W // patch)
     K = 3 * patch * patch
     _need(w2d.dtype == torch.bfloat16 and w2d.is_contiguous() and w2d.shape[0] == d and w2d.shape[1] >= K, "vit_tokens: bad weight")
@@ -432,6 +488,8 @@ def vit_tokens(imgs: Tensor, w2d: Tensor, bias: Tensor, pe: Tensor, cls: Tensor 
     if cls is not None:
         _need(cls.dtype == torch.float32 and cls.numel() == d and cls.is_contiguous(), "vit_tokens: cls f32 (d)")
     out = torch.empty((N, L + (cls is not None), d), dtype=torch.bfloat16, device=imgs.device)
+    if _empty("vit_tokens", N, L, d):
+        return out
     if patch == 16 and w2d.shape[1] == K:
         rc = _launch("vit_tokens", float(imgs.numel() * 4 + out.numel() * 2), lambda: lib().pm_vit_tokens(
             imgs.data_ptr(), w2d.data_ptr(), bias.data_ptr(), pe.data_ptr(),
@@ -454,6 +512,8 @@ def linear_strided(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_batch
     _cuda(x, w, bias, resid, out)
     args, out = _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out)
     N = w.shape[0]
+    if _empty("linear_strided", M, N, K):
+        return out
     rc = _launch("linear_bf16", 2.0 * M * N * K, lambda: lib().pm_linear_bf16_ws(*args, _stream()))
     check(rc, f"pm_linear_bf16_ws(M={M}, N={N}, K={K})")
     return out
@@ -492,6 +552,8 @@ def linear_strided_plan(x: Tensor, *, M: int, K: int, row_stride: int, rows_per_
     """linear_plan for the window form: pm_linear_bf16_plan on the arguments linear_strided() would pass (built by the same
     function).  Host arithmetic only; the tensors may live on the CPU."""
     args, _ = _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, bias, act, resid, resid_period, out_dtype, out)
+    if _empty("linear_strided_plan", *args[14:17]):
+        return 0
     return int(lib().pm_linear_bf16_plan(*args))
 
 
@@ -506,11 +568,14 @@ def w2v_stem0(x: Tensor, w: Tensor, bias: Tensor | None, norm: str, gamma: Tenso
         _need(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == w.shape[0]), "w2v_stem0: f32 (C0) vectors")
     B, L = x.shape
     C0, k = w.shape
-    _need(L >= k, f"w2v_stem0: waveform shorter than the kernel ({L} < {k})")
+    _need(L >= k and stride > 0, f"w2v_stem0: waveform shorter than the kernel ({L} < {k})")
     T0 = (L - k) // stride + 1
+    empty = _empty("w2v_stem0", B, L, C0, k)
     mode = {"none": 0, "layer": 1, "instance": 2}[norm]
     out = torch.empty((B, T0, C0), dtype=torch.bfloat16, device=x.device)
     partials = stats = None
+    if empty:
+        return out
     if mode == 2:
         partials = torch.empty(int(lib().pm_w2v_stem0_scratch_floats(B, T0)), dtype=torch.float32, device=x.device)
         stats = torch.empty((B, C0, 2), dtype=torch.float32, device=x.device)
@@ -527,9 +592,11 @@ def group_windows(x: Tensor, groups: int, cgp: int, pad_left: int, pad_right: in
     _cuda(x)
     _need(x.dim() == 3 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1), "group_windows: (B, T, d) rows")
     B, T, d = x.shape
-    _need(d % groups == 0, "group_windows: d must divide into the groups")
+    _need(groups > 0 and d % groups == 0, "group_windows: d must divide into the groups")
     cg = d // groups
     out = torch.empty((B, groups, pad_left + T + pad_right, cgp), dtype=torch.bfloat16, device=x.device)
+    if _empty("group_windows", B, T, d, cgp):
+        return out
     rc = _launch("group_windows", float(x.numel() * x.element_size() + out.numel() * 2), lambda: lib().pm_group_windows(
         x.data_ptr(), x.stride(1), _dt(x), out.data_ptr(), B, T, groups, cg, cgp, pad_left, pad_right, _stream()))
     check(rc, f"pm_group_windows(B={B}, T={T}, d={d}, G={groups})")
@@ -549,6 +616,7 @@ def grouped_conv(xg: Tensor, w: Tensor, bias: Tensor | None, k: int, stride: int
     B, G, Tp, cgp = xg.shape
     _need(w.dtype == torch.bfloat16 and w.is_contiguous() and w.shape[:2] == (G, cg), "grouped_conv: w must be contiguous bf16 (G, cg, Kp)")
     Kp = w.shape[2]
+    _need(stride > 0 and Tp >= k, f"grouped_conv: {Tp} padded steps are fewer than the {k} taps")
     To = (Tp - k) // stride + 1
     d = G * cg
     if bias is not None:
@@ -556,6 +624,8 @@ def grouped_conv(xg: Tensor, w: Tensor, bias: Tensor | None, k: int, stride: int
     if resid is not None:
         _need(resid.dtype == torch.bfloat16 and resid.shape == (B * To, d) and resid.stride(1) == 1, "grouped_conv: resid bf16 (B*To, d)")
     out = torch.empty((B * To, d), dtype=torch.bfloat16, device=xg.device)
+    if _empty("grouped_conv", B, G, To, cg, cgp, k, Kp):
+        return out
     rc = _launch("grouped_conv", 2.0 * B * To * d * k * cg, lambda: lib().pm_grouped_conv_bf16(
         xg.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
         resid.data_ptr() if resid is not None else None, resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0),
@@ -570,6 +640,8 @@ def avgpool_time2(x: Tensor) -> Tensor:
     _need(x.dim() == 3 and x.dtype == torch.bfloat16 and x.is_contiguous(), "avgpool_time2: contiguous bf16 (B, T, d)")
     B, T, d = x.shape
     out = torch.empty((B, T // 2, d), dtype=torch.bfloat16, device=x.device)
+    if _empty("avgpool_time2", B, T // 2, d):
+        return out
     rc = _launch("avgpool_time2", float(3 * out.numel() * 2), lambda: lib().pm_avgpool_time2(x.data_ptr(), out.data_ptr(), B, T, d, _stream()))
     check(rc, f"pm_avgpool_time2(B={B}, T={T}, d={d})")
     return out
@@ -634,10 +706,13 @@ def stft_mel(x: Tensor, tables, n_fft: int, hop: int, n_frames: int, mode: int, 
                           and col.dim() == 1 and val.shape == col.shape and ptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()),
           "stft_mel: csr must be mel_csr's contiguous (int32 (n_mels + 1), int32 (nnz), f32 (nnz))")
     lead, T = x.shape[:-1], x.shape[-1]
+    _need(T > 0, "stft_mel: an empty waveform (T = 0) has no frames")
     x2 = x.reshape(-1, T).float().contiguous()
     B = x2.shape[0]
     rows = n_fft // 2 + 1 if mode == 0 else n_mels
-    out = torch.empty((B, rows, n_frames), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, rows, max(n_frames, 0)), dtype=torch.float32, device=x.device)
+    if _empty("stft_mel", B * n_frames, T, rows, n_fft, hop, tables[0].numel()) or (csr is not None and _empty("stft_mel", 1, col.numel())):
+        return out.view(*lead, rows, n_frames)
     peak = torch.empty(max(B, 1), dtype=torch.int32, device=x.device) if mode == 2 else None
     fn = lib().pm_stft_mel_folded if len(tables) > 2 and tables[2] else lib().pm_stft_mel
     rc = _launch("stft_mel", float(x2.numel() * 4 + out.numel() * 4), lambda: fn(
@@ -662,6 +737,8 @@ def whisper_stem1(x: Tensor, w1: Tensor, b1: Tensor) -> Tensor:
     _need(w1.dtype == torch.bfloat16 and w1.is_contiguous() and K % 3 == 0 and K // 3 >= C, "whisper_stem1: bad packed weight")
     _need(b1.dtype == torch.float32 and b1.numel() == d and b1.is_contiguous(), "whisper_stem1: bias must be contiguous f32 (d)")
     out = torch.empty((B, T + 2, d), dtype=torch.bfloat16, device=x.device)
+    if _empty("whisper_stem1", B, C, T, d, K):
+        return out
     rc = _launch("whisper_stem1", float(x.numel() * 4 + out.numel() * 2), lambda: lib().pm_whisper_stem1(
         x.data_ptr(), w1.data_ptr(), b1.data_ptr(), out.data_ptr(), B, C, K // 3, T, d, _stream()))
     check(rc, f"pm_whisper_stem1(B={B}, C={C}, T={T}, d={d})")
@@ -681,6 +758,7 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
     B, L = tokens.shape
     V, d = emb.shape
     _need(emb.dtype in (torch.bfloat16, torch.float32) and emb.is_contiguous(), "embed_tokens: emb bf16 or f32 (V, d)")
+    empty = _empty("embed_tokens", B * L, V, d)
     # nn.Embedding raises on an id outside [0, V) (whisper.py:48); the kernel clamps so that a bad id cannot fault, so
     # the range is checked here (skipped inside a graph capture, where the caller has validated the example inputs eagerly
     # during the warm-up pass)
@@ -696,6 +774,8 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
     if emb.dtype == torch.float32:  # fp32 table -> fp32 rows
         _need(out is None, "embed_tokens: out= goes with a bf16 table")
         out = torch.empty((B, L, d), dtype=torch.float32, device=emb.device)
+        if empty:
+            return out
         rc = lib().pm_embed_tokens_f32(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr() if pos is not None else None, out.data_ptr(),
                                        B, L, pos0, d, V, _stream())
         check(rc, f"pm_embed_tokens_f32(B={B}, L={L}, d={d})")
@@ -703,6 +783,8 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
     if out is None:
         out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
     _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens: out must be contiguous (B, L, d)")
+    if empty:
+        return out
     rc = lib().pm_embed_tokens(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr() if pos is not None else None, out.data_ptr(), _dt(out), B, L, pos0, d, V,
                                _stream())
     check(rc, f"pm_embed_tokens(B={B}, L={L}, d={d})")
@@ -725,6 +807,7 @@ def _dec_rows(who: str, x: Tensor, w: Tensor, bias: Tensor | None, resid: Tensor
     if ln is not None:
         _need(all(isinstance(t, Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == K for t in ln[:2]),
               f"{who}: ln must be (gamma, beta, eps) with contiguous f32 (K) vectors")
+    _rows(who, M, N, K)
     return M, N, K
 
 
@@ -794,6 +877,7 @@ def _dec_qkv(who: str, q: Tensor, k: Tensor, v: Tensor) -> tuple[int, int, int]:
           and v.stride() == k.stride() and k.stride(3) == 1, f"{who}: k / v must be bf16 (B, H, T, 64) caches with one layout and unit last stride")
     B, H, T, _ = k.shape
     _need(q.dtype == torch.float32 and q.shape == (B, H * 64) and q.is_contiguous(), f"{who}: q must be contiguous f32 (B, H*64)")
+    _rows(who, B, H, T)
     return B, H, T
 
 
@@ -815,11 +899,12 @@ def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int
     _need(kc.dim() == 4 and kc.shape[3] == 64 and kc.shape[1] == n_heads and vc.shape == kc.shape and vc.stride() == kc.stride()
           and kc.stride(3) == 1, "prefill_attention: caches must be (B, H, T, 64) with one layout and unit last stride")
     B, H, T, _ = kc.shape
-    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1 and B > 0 and qkv.shape[0] % B == 0 and qkv.shape[0] > 0,
+    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1
+          and (qkv.shape[0] % B == 0 and qkv.shape[0] > 0 if B > 0 else qkv.shape[0] == 0),
           "prefill_attention: qkv must be (B * C, 3 * H * 64) rows with unit last stride, C >= 1")
     for t in (qkv, kc, vc):
         _need(t.dtype == torch.bfloat16, "prefill_attention: bf16 operands (fp32 caches keep the token-by-token prompt)")
-    C = qkv.shape[0] // B
+    C = qkv.shape[0] // B if B else 0
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
@@ -827,6 +912,8 @@ def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int
         raise ValueError("prefill_attention: rows of out overlap")
     _need(_apart(kc) and _apart(vc), "prefill_attention: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention: out must be bf16 (B * C, H * 64)")
+    if _empty("prefill_attention", B, H, T):
+        return out
     kv = plan.cache_kv(kc, vc)
     rc = _launch("prefill_attention", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_bf16(
         *plan.prefill_attention_args(qkv, kv, out, B, H, C, p0, T)[:-1], _stream()))
@@ -859,12 +946,13 @@ def prefill_attention_ragged(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, 
     _need(kc.dim() == 4 and kc.shape[3] == 64 and kc.shape[1] == n_heads and vc.shape == kc.shape and vc.stride() == kc.stride()
           and kc.stride(3) == 1, "prefill_attention_ragged: caches must be (B, H, T, 64) with one layout and unit last stride")
     B, H, T, _ = kc.shape
-    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1 and B > 0 and qkv.shape[0] % B == 0 and qkv.shape[0] > 0,
+    _need(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.stride(1) == 1
+          and (qkv.shape[0] % B == 0 and qkv.shape[0] > 0 if B > 0 else qkv.shape[0] == 0),
           "prefill_attention_ragged: qkv must be (B * C, 3 * H * 64) rows with unit last stride, C >= 1")
     for t in (qkv, kc, vc):
         _need(t.dtype == torch.bfloat16, "prefill_attention_ragged: bf16 operands")
     _key_start(key_start, B, "prefill_attention_ragged")
-    C = qkv.shape[0] // B
+    C = qkv.shape[0] // B if B else 0
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention_ragged: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
@@ -872,6 +960,8 @@ def prefill_attention_ragged(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, 
         raise ValueError("prefill_attention_ragged: rows of out overlap")
     _need(_apart(kc) and _apart(vc), "prefill_attention_ragged: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention_ragged: out must be bf16 (B * C, H * 64)")
+    if _empty("prefill_attention_ragged", B, H, T):
+        return out
     kv = plan.cache_kv(kc, vc)
     rc = _launch("prefill_attention_ragged", 2.0 * B * H * C * (2 * p0 + C) * 64, lambda: lib().pm_prefill_attention_ragged_bf16(
         *plan.ragged_prefill_attention_args(qkv, kv, out, B, H, C, p0, T, key_start)[:-1], _stream()))
@@ -888,6 +978,7 @@ def embed_tokens_ragged(tokens: Tensor, emb: Tensor, pos: Tensor, key_start: Ten
     B, L = tokens.shape
     V, d = emb.shape
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous(), "embed_tokens_ragged: emb bf16 (V, d)")
+    empty = _empty("embed_tokens_ragged", B * L, V, d)
     _key_start(key_start, B, "embed_tokens_ragged")
     if EMBED_CHECK_IDS and tokens.numel() and not torch.cuda.is_current_stream_capturing():
         if bool(((tokens < 0) | (tokens >= V)).any()):
@@ -898,6 +989,8 @@ def embed_tokens_ragged(tokens: Tensor, emb: Tensor, pos: Tensor, key_start: Ten
     if out is None:
         out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
     _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens_ragged: out must be contiguous (B, L, d)")
+    if empty:
+        return out
     rc = lib().pm_embed_tokens_ragged(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr(), key_start.data_ptr(), out.data_ptr(), _dt(out),
                                       B, L, pos0, d, V, _stream())
     check(rc, f"pm_embed_tokens_ragged(B={B}, L={L}, d={d})")
@@ -911,6 +1004,7 @@ def dec_embed_ragged(tok_cur: Tensor, emb: Tensor, pos_tab: Tensor, pos: Tensor,
           and pos_tab.is_contiguous() and pos_tab.shape[1] == emb.shape[1] and pos.numel() == 1,
           "dec_embed_ragged: contiguous tok_cur (B,), emb (V, d), pos_tab (rows, d); pos is one device int32")
     B = tok_cur.shape[0]
+    _rows("dec_embed_ragged", B, emb.shape[0], emb.shape[1], pos_tab.shape[0])
     _key_start(key_start, B, "dec_embed_ragged")
     _need(emb.dtype == torch.bfloat16 and pos_tab.dtype == torch.float32 and pos.dtype == torch.int32 and tok_cur.dtype == torch.int64,
           "dec_embed_ragged: bf16 table, f32 positions, int32 position, int64 tokens")
@@ -929,6 +1023,7 @@ def _tail_state(what: str, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens:
           f"{what}: contiguous int64 prompt (B, P), tokens (B, Ttot >= P), tok_cur (B,)")
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
           and pos_tab.shape[1] == emb.shape[1], f"{what}: bf16 table, f32 positions")
+    _rows(what, B, prompt.shape[1], tokens.shape[1], emb.shape[0], emb.shape[1], pos_tab.shape[0])
     # (a validation that reads *pos back: not under capture, where the position is whatever the replay finds there)
     _need(capturing() or 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: the positional table must cover position + 1")
 
@@ -944,6 +1039,7 @@ def dec_next_token(ws_val: Tensor, ws_idx: Tensor, pos: Tensor, prompt: Tensor, 
     V, d = emb.shape
     _need(ws_val.dtype == torch.float32 and ws_idx.dtype == torch.int32 and ws_val.shape == ws_idx.shape and ws_val.shape[0] == B
           and ws_val.is_contiguous() and ws_idx.is_contiguous(), "dec_next_token: ws_val f32 / ws_idx int32 (B, n_tiles)")
+    _rows("dec_next_token", B, ws_val.shape[1])
     _need(margins is None or (margins.dtype == torch.float32 and margins.shape == tokens.shape and margins.is_contiguous()),
           "dec_next_token: margins f32 like tokens")
     x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
@@ -992,6 +1088,7 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
     _need(tokens.dim() == 2 and tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.shape[0] == logits.shape[0],
           "dec_whisper_rules: tokens int64 (B, Ttot)")
     _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_whisper_rules: pos is one device int32")
+    _rows("dec_whisper_rules", logits.shape[0], logits.shape[1], tokens.shape[1])
     i32 = dict(dtype=torch.int32, device=logits.device)
     sup, blk = torch.tensor(list(suppress), **i32), torch.tensor(list(blank), **i32)
     B, V = logits.shape
@@ -1022,6 +1119,7 @@ def dec_beam_topw(logits: Tensor, scores: Tensor, finished: Tensor, pos: Tensor,
           "dec_beam_topw: logits f32 (B * W, V)")
     _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_beam_topw: pos is one device int32")
     V = logits.shape[1]
+    _rows("dec_beam_topw", B, W, V)
     cs = torch.empty(B * W, W, dtype=torch.float32, device=logits.device)
     ct = torch.empty(B * W, W, dtype=torch.int32, device=logits.device)
     rc = lib().pm_dec_beam_topw(logits.data_ptr(), logits.stride(0), V, W, scores.data_ptr(), finished.data_ptr(),
@@ -1053,6 +1151,7 @@ def dec_beam_select(cand_score: Tensor, cand_tok: Tensor, scores: Tensor, finish
           and x.is_contiguous(), "dec_beam_select: emb bf16 (V, d), pos f32 (>= Ttot, d), x f32 (B * W, d)")
     _need(pos.dtype == torch.int32 and pos.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1,
           "dec_beam_select: pos and ticket are one device int32 each")
+    _rows("dec_beam_select", B, W, V, d, tokens.shape[1], prompt.shape[1])
     rc = lib().pm_dec_beam_select(cand_score.data_ptr(), cand_tok.data_ptr(), W, scores.data_ptr(), finished.data_ptr(),
                                   parents.data_ptr(), -1 if eos is None else eos, tokens.data_ptr(), tokens.shape[1], pos.data_ptr(),
                                   prompt.data_ptr(), prompt.shape[1], tok_cur.data_ptr(), emb.data_ptr(), pos_tab.data_ptr(),
@@ -1072,6 +1171,7 @@ def dec_beam_reorder(caches: list[Tensor], parents: Tensor, pos: Tensor) -> None
     c0 = caches[0]
     _need(c0.dim() == 4 and c0.shape[0] == B * W and c0.shape[3] == 64 and c0.dtype in (torch.bfloat16, torch.float32),
           "dec_beam_reorder: caches (B * W, H, Tmax, 64) bf16 or f32")
+    _rows("dec_beam_reorder", B, W, c0.shape[1], c0.shape[2])
     _need(int(pos.item()) <= c0.shape[2], "dec_beam_reorder: position beyond the caches")
     for c in caches:
         _need(c.shape == c0.shape and c.dtype == c0.dtype and c.is_contiguous() and c.data_ptr() % 16 == 0,
@@ -1100,6 +1200,8 @@ def dwconv7_ln(x: Tensor, w: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, 
         _f32vec(t, C, f"dwconv7_ln: {nm}")
     ldy = ldy if ldy is not None else -(-C // 64) * 64
     out = torch.empty((N * H * W, ldy), dtype=out_dtype, device=x.device)
+    if _empty("dwconv7_ln", N, H, W, C):
+        return out
     nbytes = float(x.numel() * x.element_size() + out.numel() * out.element_size())
     rc = _launch("dwconv7_ln", (98.0 * x.numel(), nbytes), lambda: lib().pm_dwconv7_ln(
         x.data_ptr(), _dt(x), w.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), ldy,
@@ -1120,6 +1222,8 @@ def ln_space_to_depth(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dt
     _f32vec(beta, C, "ln_space_to_depth: beta")
     ldy = ldy if ldy is not None else -(-4 * C // 64) * 64
     out = torch.empty((N * (H // 2) * (W // 2), ldy), dtype=out_dtype, device=x.device)
+    if _empty("ln_space_to_depth", N, H, W, C):
+        return out
     nbytes = float(x.numel() * x.element_size() + out.numel() * out.element_size())
     rc = _launch("ln_space_to_depth", (0.0, nbytes), lambda: lib().pm_ln_space_to_depth(
         x.data_ptr(), x.stride(2), _dt(x), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), ldy, _dt(out), N, H, W, C,
@@ -1141,6 +1245,8 @@ def convnext_stem(imgs: Tensor, wt: Tensor, bias: Tensor, gamma: Tensor, beta: T
         _f32vec(t, d, f"convnext_stem: {nm}")
     N, _, H, W = imgs.shape
     out = torch.empty((N, H // 4, W // 4, d), dtype=out_dtype, device=imgs.device)
+    if _empty("convnext_stem", N, H // 4, W // 4, d):
+        return out
     flops = 2.0 * 48 * d * out.numel() / d
     nbytes = float(imgs.numel() * 4 + out.numel() * out.element_size())
     rc = _launch("convnext_stem", (flops, nbytes), lambda: lib().pm_convnext_stem(
@@ -1158,6 +1264,8 @@ def mean_ln(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: torch
     _f32vec(gamma, C, "mean_ln: gamma")
     _f32vec(beta, C, "mean_ln: beta")
     out = torch.empty((N, C), dtype=out_dtype, device=x.device)
+    if _empty("mean_ln", N, HW, C):
+        return out
     rc = _launch("mean_ln", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_mean_ln(
         x.data_ptr(), x.stride(1), _dt(x), gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), _dt(out), N, HW, C,
         _stream()))
@@ -1190,6 +1298,8 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, N: int, H: int, W: int, n_
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("window_attention: rows of out overlap")
     _need(out.dtype == torch.bfloat16 and out.shape[0] == M and out.shape[1] >= D and out.stride(1) == 1, "window_attention: bad out")
+    if _empty("window_attention", N, H, W, n_heads, ws):
+        return out
     nbytes = float(M * D * 2 * 4)
     rc = _launch("window_attention", (4.0 * M * L * D, nbytes), lambda: lib().pm_window_attention_bf16(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0),
@@ -1216,6 +1326,8 @@ def dwconv3_bn_act(x: Tensor, w: Tensor, scale: Tensor, shift: Tensor, stride: i
     Ho, Wo = (H, W) if stride == 1 else ((H - 2) // 2 + 1, (W - 2) // 2 + 1)
     y = torch.empty((N, Ho, Wo, C), dtype=out_dtype or x.dtype, device=x.device) if write_y else None
     ps = torch.empty((N, Ho, C), dtype=torch.float32, device=x.device) if want_psum else None
+    if _empty("dwconv3_bn_act", N, Ho, Wo, C):
+        return (y, ps) if write_y and want_psum else (y if write_y else ps)
     nbytes = float(x.numel() * x.element_size() + (y.numel() * y.element_size() if y is not None else 0))
     rc = _launch("dwconv3_bn_act", (18.0 * N * Ho * Wo * C, nbytes), lambda: lib().pm_dwconv3_bn_act(
         x.data_ptr(), _dt(x), w.data_ptr(), scale.data_ptr(), shift.data_ptr(), gate.data_ptr() if gate is not None else None,
@@ -1239,6 +1351,8 @@ def se_gate(psum: Tensor, hw: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tenso
     _f32vec(b1, R, "se_gate: b1")
     _f32vec(b2, C, "se_gate: b2")
     gate = torch.empty((N, C), dtype=torch.float32, device=psum.device)
+    if _empty("se_gate", N, T, C, R, hw):
+        return gate
     rc = _launch("se_gate", (4.0 * N * C * R, float(psum.numel() * 4)), lambda: lib().pm_se_gate(
         psum.data_ptr(), T, hw, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), gate.data_ptr(), N, C, R, _stream()))
     check(rc, f"pm_se_gate(N={N}, T={T}, C={C}, R={R})")
@@ -1258,6 +1372,8 @@ def maxvit_stem(imgs: Tensor, wt: Tensor, shift: Tensor, out_dtype: torch.dtype 
     Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
     ldy = ldy or d
     out = torch.empty((N, Ho, Wo, ldy), dtype=out_dtype, device=imgs.device)
+    if _empty("maxvit_stem", N, Ho, Wo, d):
+        return out
     rc = _launch("maxvit_stem", (54.0 * N * Ho * Wo * d, float(imgs.numel() * 4 + out.numel() * out.element_size())),
                  lambda: lib().pm_maxvit_stem(imgs.data_ptr(), wt.data_ptr(), shift.data_ptr(), out.data_ptr(), ldy, _dt(out), N, H, W,
                                               d, _stream()))
@@ -1273,6 +1389,8 @@ def im2col3x3(x: Tensor, out_dtype: torch.dtype | None = None, ldy: int | None =
     N, H, W, C = x.shape
     ldy = ldy if ldy is not None else -(-9 * C // 64) * 64
     out = torch.empty((N * H * W, ldy), dtype=out_dtype or x.dtype, device=x.device)
+    if _empty("im2col3x3", N, H, W, C):
+        return out
     rc = _launch("im2col3x3", (0.0, float(x.numel() * x.element_size() + out.numel() * out.element_size())), lambda: lib().pm_im2col3x3_nhwc(
         x.data_ptr(), _dt(x), out.data_ptr(), ldy, _dt(out), N, H, W, C, _stream()))
     check(rc, f"pm_im2col3x3_nhwc(N={N}, H={H}, W={W}, C={C}, ldy={ldy})")
@@ -1285,6 +1403,8 @@ def avgpool2x2(x: Tensor, out_dtype: torch.dtype | None = None) -> Tensor:
     _need(x.dim() == 4 and x.is_contiguous(), "avgpool2x2: x must be contiguous (N, H, W, C)")
     N, H, W, C = x.shape
     out = torch.empty((N, H // 2, W // 2, C), dtype=out_dtype or x.dtype, device=x.device)
+    if _empty("avgpool2x2", N, H // 2, W // 2, C):
+        return out
     rc = _launch("avgpool2x2", (0.0, float(x.numel() * x.element_size() + out.numel() * out.element_size())), lambda: lib().pm_avgpool2x2_nhwc(
         x.data_ptr(), _dt(x), out.data_ptr(), _dt(out), N, H, W, C, _stream()))
     check(rc, f"pm_avgpool2x2_nhwc(N={N}, H={H}, W={W}, C={C})")
@@ -1309,6 +1429,8 @@ def conv_bf16(x: Tensor, w: Tensor, bias: Tensor | None, stride: int = 1, relu: 
     out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
     _need(resid is None or (resid.shape == out.shape and resid.dtype == torch.bfloat16 and resid.is_contiguous()),
           "conv_bf16: resid must be bf16 of the output's shape")
+    if _empty("conv_bf16", N, Ho, Wo, Cin, Cout):
+        return out
     rc = _launch("conv_bf16", (2.0 * N * Ho * Wo * Cout * kh * kw * Cin, float(2 * (x.numel() + w.numel() + out.numel() * (2 if resid is not None else 1)))),
                  lambda: lib().pm_conv_bf16(x.data_ptr(), N, H, W, Cin, w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                             resid.data_ptr() if resid is not None else None, out.data_ptr(), Cout, kh, stride,
@@ -1331,6 +1453,8 @@ def resnet_stem(imgs: Tensor, wt: Tensor, shift: Tensor) -> Tensor:
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     conv_map = torch.empty((N, Hc, Wc, 64), dtype=torch.bfloat16, device=imgs.device)
     out = torch.empty((N, Hp, Wp, 64), dtype=torch.bfloat16, device=imgs.device)
+    if _empty("resnet_stem", N, H, W):
+        return out
     rc = _launch("resnet_stem", (2.0 * 147 * 64 * N * Hc * Wc, float(imgs.numel() * 4 + 4 * conv_map.numel() + 2 * out.numel())),
                  lambda: lib().pm_resnet_stem(imgs.data_ptr(), wt.data_ptr(), shift.data_ptr(), conv_map.data_ptr(), out.data_ptr(),
                                               N, H, W, _stream()))
@@ -1348,10 +1472,12 @@ def attention_hd32(q: Tensor, k: Tensor, v: Tensor, n_heads: int) -> Tensor:
     Lk = k.shape[1]
     _need(D == n_heads * 32, f"attention_hd32: head dim must be 32 (got {D} / {n_heads})")
     _need(k.shape == (B, Lk, D) and v.shape == (B, Lk, D), "attention_hd32: shape mismatch")
-    _need(Lq >= 1 and Lk >= 1, "attention_hd32: empty sequence")
+    _need(Lk >= 1 and n_heads >= 1, "attention_hd32: empty sequence")
     for t in (q, k, v):
         _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention_hd32: bf16 operands with unit last stride")
     out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
+    if _empty("attention_hd32", B * Lq, Lk, D):
+        return out
     rc = _launch("attention_hd32", 4.0 * B * n_heads * Lq * Lk * 32, lambda: lib().pm_attention_hd32_bf16(
         q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
         out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, _stream()))
@@ -1402,6 +1528,7 @@ def mixer_token_mix(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, w1f: 
     Dt = b1.numel()
     _need(C % 64 == 0 and C >= 64, f"mixer_token_mix: d_model must be a multiple of 64, got {C}")
     _need(Dt % 32 == 0 and Dt >= 32, f"mixer_token_mix: the token-mixing hidden width must be a multiple of 32, got {Dt}")
+    _need(T > 0, "mixer_token_mix: an image without tokens (T = 0)")
     _need(mixer_token_mix_supported(T, Dt, C),
           f"mixer_token_mix: T={T} tokens with hidden width {Dt} do not fit: 64 channels of LN(x) and of the hidden activations, "
           f"64 * 2 * ((T rounded up to 16) + 8 + Dt + 8) bytes, must fit the 160 KiB LDS")
@@ -1418,6 +1545,8 @@ def mixer_token_mix(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, w1f: 
         out = torch.empty_like(x)
     _need(out.shape == x.shape and out.dtype == torch.bfloat16 and out.is_contiguous(), "mixer_token_mix: out must be like x")
     rows = torch.empty((N * T, C // 64, 2), dtype=torch.float32, device=x.device) if want_row_stats else None
+    if _empty("mixer_token_mix", N, T, C, Dt):
+        return (out, rows) if want_row_stats else out
     work = (4.0 * N * C * w1f.shape[1] * 16 * Dt, float(4 * x.numel() + 2 * (w1f.numel() + w2f.numel())))
     rc = _launch("mixer_token_mix", work, lambda: lib().pm_mixer_token_mix_bf16(
         x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w1f.data_ptr(), b1.data_ptr(), w2f.data_ptr(),
@@ -1432,6 +1561,8 @@ def row_stats(x: Tensor, eps: float) -> Tensor:
     _need(x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= 1, "row_stats: x must be (M, C) rows")
     M, C = x.shape
     stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    if _empty("row_stats", M, C):
+        return stats
     rc = _launch("row_stats", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_row_stats(
         x.data_ptr(), x.stride(0) if M > 1 else C, _dt(x), stats.data_ptr(), M, C, float(eps), _stream()))
     check(rc, f"pm_row_stats(M={M}, C={C})")
@@ -1448,6 +1579,8 @@ def ln_mean(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, out_dtype: to
     _f32vec(beta, C, "ln_mean: beta")
     _need(N <= 65535, "ln_mean: at most 65535 images per call")
     out = torch.empty((N, C), dtype=out_dtype, device=x.device)
+    if _empty("ln_mean", N, T, C):
+        return out
     rc = _launch("ln_mean", (0.0, float(x.numel() * x.element_size())), lambda: lib().pm_ln_mean(
         x.data_ptr(), _dt(x), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), _dt(out), N, T, C, _stream()))
     check(rc, f"pm_ln_mean(N={N}, T={T}, C={C})")
@@ -1465,6 +1598,8 @@ def transpose_add_f32(x: Tensor, resid: Tensor | None = None, ldy: int | None = 
     _need(resid is None or (resid.shape == (N, Cc, R) and resid.dtype == torch.float32 and resid.stride() == (Cc * ldy, ldy, 1)),
           "transpose_add_f32: resid must be f32 (N, Cc, R) with the output's strides")
     out = torch.empty((N, Cc, ldy), dtype=torch.float32, device=x.device)[:, :, :R]
+    if _empty("transpose_add_f32", N, R, Cc):
+        return out
     rc = _launch("transpose_add_f32", (0.0, float(x.numel() * 4 * (3 if resid is not None else 2))), lambda: lib().pm_transpose_add_f32(
         x.data_ptr(), resid.data_ptr() if resid is not None else None, out.data_ptr(), ldy, N, R, Cc, _stream()))
     check(rc, f"pm_transpose_add_f32(N={N}, R={R}, Cc={Cc})")
@@ -1493,6 +1628,7 @@ def conv1d_f32(x: Tensor, w: Tensor, bias: Tensor | None, *, k: int, stride: int
     _f32c(w, "conv1d_f32: w")
     _need(w.dim() == 2 and w.shape[1] == k * Cin and w.shape[0] % up == 0, f"conv1d_f32: w {tuple(w.shape)} is not (up * Cout, {k} * {Cin})")
     Cout = w.shape[0] // up
+    empty = _empty("conv1d_f32", B, Tin, Cin, Cout, k, stride)
     _need(conv1d_supported(Tin, Cin, Cout, k, stride, left, right, zero_pad, up),
           f"conv1d_f32: {Tin} frames with padding ({left}, {right}), kernel {k}, stride {stride} are not served (reflect padding must be shorter than the clip)")
     Mr = (Tin + left + right - k) // stride + 1
@@ -1504,6 +1640,8 @@ def conv1d_f32(x: Tensor, w: Tensor, bias: Tensor | None, *, k: int, stride: int
         _need(resid.shape == (B, Tout, Cout) and up == 1 and trim == 0, "conv1d_f32: resid must be (B, Tout, Cout)")
         _f32c(resid, "conv1d_f32: resid")
     out = torch.empty((B, Tout, Cout), dtype=torch.float32, device=x.device)
+    if empty:
+        return out
     rc = _launch("conv1d_f32", 2.0 * B * Mr * w.shape[0] * w.shape[1], lambda: lib().pm_conv1d_f32(
         x.data_ptr(), x.stride(0) if B > 1 else Tin * Cin, w.data_ptr(), bias.data_ptr() if bias is not None else None,
         resid.data_ptr() if resid is not None else None, out.data_ptr(), B, Tin, Cin, Cout, k, stride, left, right, int(zero_pad),
@@ -1529,8 +1667,10 @@ def lstm_f32(x: Tensor, w_ih: list[Tensor], w_hh: list[Tensor], bias: list[Tenso
         _need(a.shape == (4 * H, H) and b_.shape == (4 * H, H) and c.shape == (4 * H,), "lstm_f32: weights must be (4H, H), input size == hidden size")
         for t in (a, b_, c):
             _f32c(t, "lstm_f32: weights")
-    work = torch.empty((lib().pm_lstm_workspace_floats(B, T, H),), dtype=torch.float32, device=x.device)
     out = torch.empty_like(x)
+    if _empty("lstm_f32", B, T, H):
+        return out
+    work = torch.empty((lib().pm_lstm_workspace_floats(B, T, H),), dtype=torch.float32, device=x.device)
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
     rc = _launch("lstm_f32", 2.0 * B * T * 8 * H * H * n, lambda: lib().pm_lstm_f32(
         x.data_ptr(), arr(w_ih), arr(w_hh), arr(bias), n, work.data_ptr(), out.data_ptr(), int(residual) | (2 if plain else 0), B, T, H, _stream()))
@@ -1548,6 +1688,8 @@ def rvq_encode(z: Tensor, codebooks: Tensor, norms: Tensor, n_q: int) -> Tensor:
     _need(1 <= n_q <= Q and norms.shape == (Q, N), f"rvq_encode: n_quantizers must be in 1..{Q}")
     M = z.shape[0]
     codes = torch.empty((n_q, M), dtype=torch.int64, device=z.device)
+    if _empty("rvq_encode", M, D, N):
+        return codes
     rc = _launch("rvq_encode_f32", 2.0 * M * N * D * n_q, lambda: lib().pm_rvq_encode_f32(
         z.data_ptr(), codebooks.data_ptr(), norms.data_ptr(), codes.data_ptr(), M, n_q, D, N, _stream()))
     check(rc, f"pm_rvq_encode_f32(M={M}, n_q={n_q}, dim={D}, codebook={N})")
@@ -1563,6 +1705,8 @@ def rvq_decode(codes: Tensor, codebooks: Tensor) -> Tensor:
     Q, N, D = codebooks.shape
     _need(1 <= n_q <= Q, f"rvq_decode: {n_q} code streams for {Q} codebooks")
     out = torch.empty((B, T, D), dtype=torch.float32, device=codes.device)
+    if _empty("rvq_decode", B, T, D, N):
+        return out
     rc = _launch("rvq_decode_f32", (0.0, float(out.numel() * 4 * (n_q + 1))), lambda: lib().pm_rvq_decode_f32(
         codes.data_ptr(), codes.stride(0), codes.stride(1), codes.stride(2), codebooks.data_ptr(), out.data_ptr(), B, T, n_q, D, N, _stream()))
     check(rc, f"pm_rvq_decode_f32(B={B}, T={T}, n_q={n_q})")
@@ -1581,6 +1725,8 @@ def groupnorm1_(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, resid: Tenso
         _need(resid.shape == x.shape, "groupnorm1_: resid must have x's shape")
         _f32c(resid, "groupnorm1_: resid")
     _need(B <= 65535 and T >= 1, "groupnorm1_: at most 65535 clips, at least one frame")
+    if _empty("groupnorm1_", B, T, C):
+        return x
     work = torch.empty((lib().pm_groupnorm1_workspace_doubles(B, T * C),), dtype=torch.float64, device=x.device)
     rc = _launch("groupnorm1_f32", (0.0, float(x.numel() * 12)), lambda: lib().pm_groupnorm1_f32(
         x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), resid.data_ptr() if resid is not None else None, work.data_ptr(), B, T * C, C,
@@ -1597,6 +1743,8 @@ def encodec_scale(x: Tensor) -> Tensor:
     B, C, T = x.shape
     _need(T >= 1 and C >= 1, "encodec_scale: empty clip")
     out = torch.empty((B, 1, 1), dtype=torch.float32, device=x.device)
+    if _empty("encodec_scale", B, C, T):
+        return out
     rc = _launch("encodec_scale_f32", (0.0, float(x.numel() * 4)), lambda: lib().pm_encodec_scale_f32(x.data_ptr(), out.data_ptr(), B, C, T, _stream()))
     check(rc, f"pm_encodec_scale_f32(B={B}, C={C}, T={T})")
     return out
@@ -1607,9 +1755,12 @@ def scale_clips(x: Tensor, scale: Tensor, divide: bool) -> Tensor:
     _cuda(x, scale)
     _f32c(x, "scale_clips: x")
     _f32c(scale, "scale_clips: scale")
-    B = x.shape[0]
-    _need(x.dim() >= 2 and scale.numel() == B and B <= 65535 and x.numel() > 0, "scale_clips: one scale per clip, at most 65535 clips")
+    _need(x.dim() >= 2, "scale_clips: x must be (B, ...)")
+    B, per_clip = x.shape[0], x.shape[1:].numel()
+    _need(scale.numel() == B and B <= 65535, "scale_clips: one scale per clip, at most 65535 clips")
     out = torch.empty_like(x)
+    if _empty("scale_clips", B, per_clip):
+        return out
     rc = _launch("scale_clips_f32", (0.0, float(x.numel() * 8)), lambda: lib().pm_scale_clips_f32(
         x.data_ptr(), scale.data_ptr(), out.data_ptr(), B, x.numel() // B, int(divide), _stream()))
     check(rc, "pm_scale_clips_f32")
@@ -1633,6 +1784,8 @@ def cls_head_gemm(x: Tensor, w: Tensor, bias: Tensor | None = None) -> Tensor:
     if bias is not None:
         _need(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == G * N, "cls_head_gemm: bias must be f32 (G * N)")
     out = torch.empty((M, G, N), dtype=torch.bfloat16, device=x.device)
+    if _empty("cls_head_gemm", M, G, N, K):
+        return out
     rc = _launch("cls_head_gemm", (2.0 * M * G * N * K, float(2 * (x2.numel() + w.numel() + out.numel()))), lambda: lib().pm_cls_head_gemm(
         x2.data_ptr(), x2.stride(0), K, w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), G * N, N,
         M, N, K, G, _stream()))
@@ -1652,6 +1805,8 @@ def cls_attend(x: Tensor, stats: Tensor | None, u: Tensor, scale: float, eps: fl
     if stats is not None:
         _need(stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape == (N * L, 2), "cls_attend: stats must be f32 (N*L, 2)")
     out = torch.empty((N, H, d), dtype=torch.bfloat16, device=x.device)
+    if _empty("cls_attend", N, L, d, H):
+        return out
     rc = _launch("cls_attend", (4.0 * N * H * L * d, float(2 * (x.numel() + 2 * u.numel()))), lambda: lib().pm_cls_attend(
         x.data_ptr(), x.stride(1), x.stride(0), stats.data_ptr() if stats is not None else None, u.data_ptr(), out.data_ptr(),
         N, L, d, H, float(scale), float(eps), _stream()))
@@ -1680,7 +1835,7 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
     _need(h.stride(1) == 1 and w.stride(1) == 1, "lm_score: h and w must be K-contiguous")
     M, K = h.shape
     V = w.shape[0]
-    _need(M >= 1 and V >= 1 and K >= 1, "lm_score: empty operand")
+    _need(V >= 1 and K >= 1, "lm_score: empty operand")
     _need(h.stride(0) % 8 == 0 and w.stride(0) % 8 == 0, "lm_score: row strides must be multiples of 8 elements")
     _need(targets.dtype == torch.int64 and targets.shape == (M,), f"lm_score: targets must be int64 ({M},)")
     targets = targets.contiguous()
@@ -1698,6 +1853,9 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
         _need(lse.dtype == torch.float32 and lse.shape == (M,) and lse.is_contiguous(), "lm_score: lse_out must be contiguous f32 (M,)")
     if am is not None:
         _need(am.dtype == torch.int32 and am.shape == (M,) and am.is_contiguous(), "lm_score: argmax_out must be contiguous int32 (M,)")
+    res = (out,) + ((lse,) if want_lse or lse_out is not None else ()) + ((am,) if want_argmax or argmax_out is not None else ())
+    if _empty("lm_score", M, V, K):
+        return res[0] if len(res) == 1 else res
     nws = lm_score_ws_bytes(M, V)
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
@@ -1707,7 +1865,6 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
         h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), targets.data_ptr(), out.data_ptr(),
         lse.data_ptr() if lse is not None else None, am.data_ptr() if am is not None else None, ws.data_ptr(), M, V, K, _stream()))
     check(rc, f"pm_lm_score_bf16(M={M}, V={V}, K={K})")
-    res = (out,) + ((lse,) if want_lse or lse_out is not None else ()) + ((am,) if want_argmax or argmax_out is not None else ())
     return res[0] if len(res) == 1 else res
 
 
@@ -1738,11 +1895,11 @@ def _align_qk(who: str, q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, fr
     _need(q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16, f"{who}: q and k must be bf16")
     B, L, inner = q.shape
     S = k.shape[1]
-    _need(B >= 1 and L >= 1 and S >= 4 and inner >= 64 and inner % 64 == 0, f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}: head dim 64 only")
+    _need(L >= 1 and S >= 4 and inner >= 64 and inner % 64 == 0, f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}: head dim 64 only")
     _need(q.stride(2) == 1 and k.stride(2) == 1, f"{who}: q and k must have unit last strides")
     _need(all(s % 8 == 0 for s in (q.stride(0), q.stride(1), k.stride(0), k.stride(1))), f"{who}: strides must be multiples of 8 elements")
     for t, n, name in ((heads, None, "heads"), (lengths, B, "lengths"), (frames, B, "frames")):
-        _need(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.numel() >= 1 and (n is None or t.numel() == n),
+        _need(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and (t.numel() >= 1 if n is None else t.numel() == n),
               f"{who}: {name} must be a contiguous int32 vector" + ("" if n is None else f" of {n}"))
     return B, L, S, inner // 64, heads.numel()
 
@@ -1756,6 +1913,8 @@ def align_lse(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tens
     if out is None:
         out = torch.empty((B, nh, L), dtype=torch.float32, device=q.device)
     _need(out.dtype == torch.float32 and out.shape == (B, nh, L) and out.is_contiguous(), f"align_lse: out must be contiguous f32 {(B, nh, L)}")
+    if _empty("align_lse", B, L, S, nh):
+        return out
     rc = _launch("align_lse", (2.0 * B * nh * L * S * 64, float(2 * B * nh * (L + S) * 64)), lambda: lib().pm_align_lse_bf16(
         q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), heads.data_ptr(), lengths.data_ptr(),
         frames.data_ptr(), out.data_ptr(), B, L, S, nh, H, _stream()))
@@ -1774,6 +1933,8 @@ def align_matrix(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: T
     _need(lse.dtype == torch.float32 and lse.shape == (B, nh, L) and lse.is_contiguous(), f"align_matrix: lse must be contiguous f32 {(B, nh, L)}")
     _need(m.dtype == torch.float32 and m.shape == (B, L, S) and m.stride(2) == 1 and m.stride(1) >= S and _apart(m),
           f"align_matrix: m must be f32 {(B, L, S)} with a unit last stride and rows that do not overlap")
+    if _empty("align_matrix", B, L, S, nh):
+        return m
     rc = _launch("align_matrix", (2.0 * B * nh * L * S * 64, float(4 * B * L * S)), lambda: lib().pm_align_matrix_bf16(
         q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), heads.data_ptr(), lengths.data_ptr(),
         frames.data_ptr(), lse.data_ptr(), m.data_ptr(), m.stride(1), m.stride(0), B, L, S, nh, H, float(inv_heads), int(bool(first)),
@@ -1790,7 +1951,7 @@ def align_dtw(m: Tensor, lengths, frames, skip_first: int = 0, skip_last: int = 
     the window.  ``out`` / ``ws`` (uint8, align_ws_bytes(B, L, S)): caller-owned buffers.  L <= 448."""
     _need(m.dim() == 3 and m.dtype == torch.float32 and m.stride(2) == 1, "align_dtw: m must be f32 (B, L, S) with a unit last stride")
     B, L, S = m.shape
-    _need(B >= 1 and 1 <= L <= ALIGN_MAX_ROWS and S >= 4, f"align_dtw: m {tuple(m.shape)}: 1 <= L <= {ALIGN_MAX_ROWS}, S >= 4")
+    _need(1 <= L <= ALIGN_MAX_ROWS and S >= 4, f"align_dtw: m {tuple(m.shape)}: 1 <= L <= {ALIGN_MAX_ROWS}, S >= 4")
     _need(m.stride(1) >= S, "align_dtw: rows of m overlap")
     _need(isinstance(skip_first, int) and isinstance(skip_last, int) and skip_first >= 0 and skip_last >= 0,
           f"align_dtw: skip_first / skip_last must be ints >= 0, got {skip_first!r}, {skip_last!r}")
@@ -1800,6 +1961,8 @@ def align_dtw(m: Tensor, lengths, frames, skip_first: int = 0, skip_last: int = 
     if out is None:
         out = torch.empty((B, L), dtype=torch.int32, device=m.device)
     _need(out.dtype == torch.int32 and out.shape == (B, L) and out.is_contiguous(), f"align_dtw: out must be contiguous int32 {(B, L)}")
+    if _empty("align_dtw", B, L, S):
+        return out
     nws = align_ws_bytes(B, L, S)
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=m.device)
@@ -1906,6 +2069,7 @@ def embed_tokens_varlen(tokens: Tensor, emb: Tensor, pos: Tensor | None, seq: Se
     V, d = emb.shape
     _need(B == seq.B and L == seq.L, f"embed_tokens_varlen: tokens {(B, L)} against lengths for {(seq.B, seq.L)}")
     _need(emb.dtype in (torch.bfloat16, torch.float32) and emb.is_contiguous(), "embed_tokens_varlen: emb bf16 or f32 (V, d)")
+    empty = _empty("embed_tokens_varlen", seq.total, V, d)
     if EMBED_CHECK_IDS and seq.total and not torch.cuda.is_current_stream_capturing():
         valid = torch.arange(L, device=tokens.device)[None, :] < (seq.cu[1:] - seq.cu[:-1])[:, None]
         bad = valid & ((tokens < 0) | (tokens >= V))
@@ -1917,6 +2081,8 @@ def embed_tokens_varlen(tokens: Tensor, emb: Tensor, pos: Tensor | None, seq: Se
     if emb.dtype == torch.float32:
         out_dtype = torch.float32
     out = torch.empty((seq.total, d), dtype=out_dtype, device=emb.device)
+    if empty:
+        return out
     rc = lib().pm_embed_tokens_varlen(tokens.data_ptr(), emb.data_ptr(), _dt(emb), pos.data_ptr() if pos is not None else None,
                                       seq.cu.data_ptr(), out.data_ptr(), _dt(out), B, L, d, V, _stream())
     check(rc, f"pm_embed_tokens_varlen(B={B}, L={L}, d={d}, T={seq.total})")
@@ -1938,6 +2104,8 @@ def rows_pack(x: Tensor, seq: SeqLens) -> Tensor:
     _seq(seq, "rows_pack", x)
     B, L, d = _padded(x, seq, "rows_pack")
     out = torch.empty((seq.total, d), dtype=x.dtype, device=x.device)
+    if _empty("rows_pack", seq.total, d):
+        return out
     rc = _launch("rows_pack", (0.0, 2.0 * seq.total * d * x.element_size()), lambda: lib().pm_rows_pack(
         x.data_ptr(), x.stride(0), x.stride(1), seq.cu.data_ptr(), out.data_ptr(), out.stride(0), B, L, d, x.element_size(), _stream()))
     check(rc, f"pm_rows_pack(B={B}, L={L}, d={d})")
@@ -1952,6 +2120,8 @@ def rows_unpack(x: Tensor, seq: SeqLens) -> Tensor:
     d, eb = x.shape[1], x.element_size()
     _need((d * eb) % 16 == 0 and (x.stride(0) * eb) % 16 == 0 and x.stride(0) >= d, "rows_unpack: rows and strides must be multiples of 16 bytes")
     out = torch.empty((seq.B, seq.L, d), dtype=x.dtype, device=x.device)
+    if _empty("rows_unpack", seq.total, d):  # no packed row at all: every padded row is a tail row
+        return out.zero_()
     rc = _launch("rows_unpack", (0.0, float(seq.total + seq.B * seq.L) * d * eb), lambda: lib().pm_rows_unpack(
         x.data_ptr(), x.stride(0), seq.cu.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), seq.B, seq.L, d, eb, _stream()))
     check(rc, f"pm_rows_unpack(B={seq.B}, L={seq.L}, d={d})")
@@ -1963,6 +2133,8 @@ def rows_zero_tail(x: Tensor, seq: SeqLens) -> Tensor:
     _seq(seq, "rows_zero_tail", x)
     B, L, d = _padded(x, seq, "rows_zero_tail")
     _need(_apart(x), "rows_zero_tail: rows of x overlap")
+    if _empty("rows_zero_tail", B * L, d):
+        return x
     rc = _launch("rows_zero_tail", (0.0, float(B * L - seq.total) * d * x.element_size()), lambda: lib().pm_rows_zero_tail(
         x.data_ptr(), x.stride(0), x.stride(1), seq.cu.data_ptr(), B, L, d, x.element_size(), _stream()))
     check(rc, f"pm_rows_zero_tail(B={B}, L={L}, d={d})")
@@ -1978,6 +2150,8 @@ def segment_mean(x: Tensor, seq: SeqLens) -> Tensor:
     _need((d * eb) % 16 == 0 and (x.stride(0) * eb) % 16 == 0 and x.stride(0) >= d and seq.B <= 65535,
           "segment_mean: rows and strides must be multiples of 16 bytes, at most 65535 sequences")
     out = torch.empty((seq.B, d), dtype=torch.float32, device=x.device)
+    if _empty("segment_mean", seq.total, d):  # no packed row at all: the mean of a sequence without rows is 0, as the kernel writes it
+        return out.zero_()
     rc = _launch("segment_mean", (float(seq.total * d), float(seq.total * d * eb)), lambda: lib().pm_segment_mean(
         x.data_ptr(), x.stride(0), _dt(x), seq.cu.data_ptr(), out.data_ptr(), seq.B, d, _stream()))
     check(rc, f"pm_segment_mean(B={seq.B}, d={d}, T={seq.total})")
@@ -2005,7 +2179,7 @@ def ctc_head(h: Tensor, w: Tensor, bias: Tensor | None = None, *, want_best_logp
     _need(h.stride(1) == 1 and w.stride(1) == 1, "ctc_head: h and w must be K-contiguous")
     M, K = h.shape
     V = w.shape[0]
-    _need(M >= 1 and K >= 8 and K % 8 == 0, f"ctc_head: M >= 1 and K a multiple of 8, got M={M}, K={K}")
+    _need(K >= 8 and K % 8 == 0, f"ctc_head: K a multiple of 8, got M={M}, K={K}")
     _need(2 <= V <= CTC_MAX_VOCAB, f"ctc_head: 2 <= V <= {CTC_MAX_VOCAB}, got {V}")
     _need(h.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and h.stride(0) >= K and w.stride(0) >= K,
           "ctc_head: row strides must be multiples of 8 elements")
@@ -2022,6 +2196,8 @@ def ctc_head(h: Tensor, w: Tensor, bias: Tensor | None = None, *, want_best_logp
     blp = best_logp_out if best_logp_out is not None else (torch.empty(M, dtype=torch.float32, device=dev) if want_best_logp else None)
     if blp is not None:
         _need(blp.dtype == torch.float32 and blp.shape == (M,) and blp.is_contiguous(), "ctc_head: best_logp_out must be contiguous f32 (M,)")
+    if _empty("ctc_head", M, V, K):
+        return out, best, blp
     ldl = max(out.stride(0), V)
     nbytes = float(2 * (h.numel() + w.numel()) + 4 * M * V + 8 * M)
     rc = _launch("ctc_head", (2.0 * M * V * K, nbytes), lambda: lib().pm_ctc_head_bf16(
@@ -2076,7 +2252,7 @@ def _ctc_rec(who: str, logp: Tensor, seq: SeqLens, targets: Tensor, target_lengt
     _ctc_frames(who, seq, logp.shape[0], logp, targets)
     T, V = logp.shape
     B, Umax = targets.shape
-    _need(B == seq.B and B >= 1, f"{who}: {B} target rows for {seq.B} clips")
+    _need(B == seq.B, f"{who}: {B} target rows for {seq.B} clips")
     _need(V >= 1 and (logp.stride(0) >= V or T <= 1), f"{who}: rows of logp overlap")
     _need(Umax <= CTC_MAX_TARGET, f"{who}: at most {CTC_MAX_TARGET} labels per clip, got {Umax}")
     _need(Umax == 0 or B == 1 or targets.stride(0) >= Umax, f"{who}: rows of targets overlap")
@@ -2097,6 +2273,8 @@ def ctc_forward(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, bla
         out = torch.empty(B, dtype=torch.float32, device=logp.device)
     _cuda(out)
     _need(out.dtype == torch.float32 and out.shape == (B,) and out.is_contiguous(), f"ctc_forward: out must be contiguous f32 ({B},)")
+    if _empty("ctc_forward", B, V):
+        return out
     rc = _launch("ctc_forward", (float(T * (2 * Umax + 1)), float(4 * T * (Umax + 1))), lambda: lib().pm_ctc_forward_f32(
         logp.data_ptr(), max(logp.stride(0), V), seq.cu.data_ptr(), targets.data_ptr() if Umax else None, max(targets.stride(0), Umax),
         tl.data_ptr(), out.data_ptr(), T, B, Umax, V, blank, _stream()))
@@ -2115,6 +2293,8 @@ def ctc_viterbi(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, bla
     stop = torch.empty((B, Umax), dtype=torch.int32, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
     Tmax = seq.max_len
+    if _empty("ctc_viterbi", B, V):
+        return start, stop, score
     nws = ctc_ws_bytes(B, Tmax, Umax)
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)

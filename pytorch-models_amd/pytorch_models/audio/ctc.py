@@ -43,6 +43,8 @@ class Wav2Vec2CTC(nn.Module):
     # ---- encoder rows -> packed log-probabilities
     def _rows(self, x: Tensor, lengths):
         """(packed final hidden rows (sum frames, d), SeqLens of the frames)"""
+        if x.dim() >= 1 and x.shape[0] == 0:  # (the CPU form has no empty batch either: it has no rows to concatenate)
+            raise ValueError(f"Wav2Vec2CTC: an empty batch of clips is refused (got {tuple(x.shape)})")
         cpu = _cpu.on_cpu(x, self.lm_head.weight)
         if not cpu and self.lm_head.weight.dtype != torch.bfloat16:
             raise NotImplementedError(

@@ -494,7 +494,7 @@ class EnCodec(nn.Module):
             raise NotImplementedError("EnCodec.decode: inference only on a HIP device (call .eval())")
         _check_codes(x, "EnCodec.decode")
         if x.dim() != 3 or not 1 <= x.shape[1] <= len(self.quantizer) or x.shape[0] < 1 or x.shape[2] < 1:
-            raise ValueError(f"EnCodec.decode: expected (B, n_q <= {len(self.quantizer)}, T) indices, got {tuple(x.shape)}")
+            raise ValueError(f"EnCodec.decode: expected (B, n_q <= {len(self.quantizer)}, T) indices, neither B nor T empty, got {tuple(x.shape)}")
         if scale is not None:
             try:
                 ops.check_devices(x, scale)

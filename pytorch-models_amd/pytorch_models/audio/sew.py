@@ -34,7 +34,7 @@ class SEW(Wav2Vec2):
         h = self.layers(self.norm(h))
         up = self.upsample[0]
         y = ops.linear(h.reshape(-1, d), _wb(up, "w", up.weight), _f32(up, "b", up.bias), act="gelu")  # (B*T/2, 2d) row-major == (B, T/2 * 2, d)
-        y = y.view(B, -1, d)
+        y = y.view(B, 2 * h.shape[1], d)
         if y.shape[1] < T:  # odd T: the dropped last frame comes back as zeros (sew.py:37-38)
             y = torch.cat([y, y.new_zeros(B, T - y.shape[1], d)], 1)
         return y.to(self.norm.weight.dtype)

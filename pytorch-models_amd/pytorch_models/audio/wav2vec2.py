@@ -94,7 +94,7 @@ class FeatureEncoder(nn.Sequential):
                                    act="gelu" if g is None else "none")
             if g is not None:
                 y = ops.layernorm(y, g, be, norm.eps, act="gelu")
-            h = y.view(B, To, -1)
+            h = y.view(B, To, y.shape[-1])
         return h
 
     def forward(self, x: Tensor) -> Tensor:

@@ -48,7 +48,7 @@ def check_args(who: str, tokens: Tensor, memory: Tensor, n_layers: int, n_heads:
         raise ValueError(f"{who}: memory must be (B = {B}, S, d), got {tuple(memory.shape)}")
     S = memory.shape[1]
     if B < 1 or L < 1 or S < 4:
-        raise ValueError(f"{who}: needs at least one clip, one token and 4 frames (tokens {tuple(tokens.shape)}, memory {tuple(memory.shape)})")
+        raise ValueError(f"{who}: an empty batch is refused: needs at least one clip, one token and 4 frames (tokens {tuple(tokens.shape)}, memory {tuple(memory.shape)})")
     hs = default_heads(n_layers, n_heads) if heads is None else [tuple(int(v) for v in p) for p in heads]
     if not hs or any(len(p) != 2 or not (0 <= p[0] < n_layers and 0 <= p[1] < n_heads) for p in hs) or len(set(hs)) != len(hs):
         raise ValueError(f"{who}: heads must be distinct (layer, head) pairs with layer < {n_layers} and head < {n_heads}, got {hs}")

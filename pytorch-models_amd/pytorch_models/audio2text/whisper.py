@@ -187,6 +187,7 @@ class WhisperDecoder(nn.Module):
         from .._hip.controls import check_controls
         from .generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
 
+        ops.refuse_empty_batch("WhisperDecoder.generate", memory, prompt)
         fp32 = self.token_embs.weight.dtype == torch.float32
         check_controls("WhisperDecoder.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size,
                        return_lengths, vocab=self.token_embs.weight.shape[0], beams=1 if beams == 1 and not return_beams else max(beams, 2),
@@ -268,6 +269,7 @@ class Whisper(nn.Module):
         from .._hip.controls import check_controls
         from .generate import check_ragged, check_sampling_tail
 
+        ops.refuse_empty_batch("Whisper.generate", x, prompt)
         check_controls("Whisper.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size,
                        return_lengths, vocab=self.decoder.token_embs.weight.shape[0],
                        beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path, kv32=exact,
@@ -352,4 +354,6 @@ class WhisperPreprocessor(MelSpectrogram):
         PER-SAMPLE max - 8, (x + 4) / 4 - all inside the two logmel kernels."""
         if _cpu.on_cpu(x, self.window, self.filters):
             return _cpu.whisper_log_mel(x, self.window, self.filters)
+        if x.numel() == 0:  # as the CPU path, whose reflect padding has no empty batch
+            raise ValueError(f"WhisperPreprocessor: an empty batch of waveforms is refused (got {tuple(x.shape)})")
         return ops.stft_mel(x, self._tables(), 400, 160, x.shape[-1] // 160, 2, self._csr(), self.filters.shape[0])

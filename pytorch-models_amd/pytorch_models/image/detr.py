@@ -96,7 +96,7 @@ class Bottleneck(nn.Module):
         w2, b2 = _conv_bn(r[3], r[4])
         w3, b3 = _conv_bn(r[6], r[7])
         stride = r[3].stride[0]
-        u = ops.linear(h.view(N * H * W, Cin), w1.view(w1.shape[0], Cin), b1, act="relu").view(N, H, W, -1)
+        u = ops.linear(h.view(N * H * W, Cin), w1.view(w1.shape[0], Cin), b1, act="relu").view(N, H, W, w1.shape[0])
         t = ops.conv_bf16(u, w2, b2, stride, relu=True)
         sc = h
         if not isinstance(self.shortcut, nn.Identity):
@@ -357,7 +357,7 @@ class DETR(nn.Module):
             query = layer.run(query, x, N, qe, pos)
         query = _norm(self.norm, query)
         cl = self.classifier
-        out["logits"] = ops.linear(query, _wb(cl, "w", cl.weight), _f32(cl, "b", cl.bias), out_dtype=torch.float32).view(N, Q, -1)
+        out["logits"] = ops.linear(query, _wb(cl, "w", cl.weight), _f32(cl, "b", cl.bias), out_dtype=torch.float32).view(N, Q, cl.weight.shape[0])
         b0, b1, b2 = self.box_head[0], self.box_head[2], self.box_head[4]
         u = ops.linear(query, _wb(b0, "w", b0.weight), _f32(b0, "b", b0.bias), act="relu")
         u = ops.linear(u, _wb(b1, "w", b1.weight), _f32(b1, "b", b1.bias), act="relu")

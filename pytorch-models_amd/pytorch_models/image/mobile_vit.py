@@ -56,9 +56,9 @@ def _conv(x: Tensor, conv: nn.Conv2d, norm: nn.BatchNorm2d | None, act: str, res
     k, s, g = conv.kernel_size[0], conv.stride[0], conv.groups
     if k == 1 and s == 1 and g == 1:  # a GEMM over the pixels
         N, H, W, C = x.shape
-        r2 = resid.reshape(N * H * W, -1) if resid is not None else None
+        r2 = resid.reshape(N * H * W, resid.shape[-1]) if resid is not None else None
         y = ops.linear(x.reshape(N * H * W, C), w.view(w.shape[0], C), b, act=act, resid=r2)
-        return y.view(N, H, W, -1)
+        return y.view(N, H, W, y.shape[-1])
     return ops.conv2d_nhwc(x, w, b, s, conv.padding[0], g, act, resid)
 
 

@@ -61,7 +61,7 @@ def score_targets(tokens: Tensor, lengths, who: str) -> Tensor:
         return tgt.contiguous()
     ops.no_capture(who, "reads lengths on the host")
     lens = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
-    if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > L:
+    if lens.numel() != B or (B and (int(lens.min()) < 1 or int(lens.max()) > L)):
         raise ValueError(f"{who}: lengths must hold {B} values in [1, {L}], got {lens.tolist()}")
     keep = torch.arange(1, L, device=tokens.device)[None, :] < lens.to(tokens.device)[:, None]
     return torch.where(keep, tgt, torch.full_like(tgt, -1))
@@ -143,6 +143,7 @@ class GPT2(nn.Module):
         from .._hip.controls import check_controls
         from ..audio2text.generate import beam_decode, check_ragged, check_sampling_tail, greedy_decode, greedy_exact
 
+        ops.refuse_empty_batch("GPT2.generate", prompt)
         check_controls("GPT2.generate", eos_token_id, pad_token_id, min_new_tokens, repetition_penalty, no_repeat_ngram_size, return_lengths,
                        vocab=self.token_embs.weight.shape[0], beams=1 if beams == 1 and not return_beams else max(beams, 2), path=path,
                        fp32=self.token_embs.weight.dtype == torch.float32)

@@ -60,7 +60,7 @@ class GEGLU(nn.Module):
             raise RuntimeError("GEGLU: HIP devices only (no CPU path)")
         xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
         h = ops.linear(xb.reshape(-1, x.shape[-1]), self._packed(), None)
-        return ops.geglu(h).view(*x.shape[:-1], -1)
+        return ops.geglu(h).view(*x.shape[:-1], h.shape[-1] // 2)
 
 
 class RelativePositionBias(nn.Module):

@@ -621,7 +621,7 @@ class EncoderLayer(DecoderLayer):
         wku, wvh, cv = sa._pack_cls(self.sa_norm)
         u = ops.cls_head_gemm(q, wku)
         ctx = ops.cls_attend(x, stats, u, sa.head_dim ** -0.5, self.sa_norm.eps)
-        o = ops.cls_head_gemm(ctx, wvh, cv).view(B, -1)
+        o = ops.cls_head_gemm(ctx, wvh, cv).view(B, d)
         y = ops.linear(o, sa.out_proj.weight, _f32(sa.out_proj, "b", sa.out_proj.bias), resid=x0)
         l1, l2 = mlp.linear1, mlp.linear2
         h = ops.linear(self.mlp_norm(y), l1.weight, _f32(l1, "b", l1.bias), act=mlp.act_name)
