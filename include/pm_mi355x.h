@@ -40,7 +40,10 @@ const char* pm_strerror(int code);
  * linear2 (transformer.py:59-66) and the residual adds of Encoder/DecoderLayer (transformer.py:98-100,
  * 124-125).  x, w: bf16, K-contiguous; bias: f32 or NULL; resid: resid_dtype or NULL; y: y_dtype.
  * Requires K % 64 == 0 and 16-byte aligned x / w rows (ld % 8 == 0).  N, ldy, ldr multiples of 4 take the
- * vector epilogue; ragged N (a 51865-row vocabulary: the tied-embedding logits of whisper.py:52) stores element-wise. */
+ * vector epilogue; ragged N (a 51865-row vocabulary: the tied-embedding logits of whisper.py:52) stores element-wise.
+ * Aliasing (all pm_linear_bf16* entry points): resid may alias y as the very same matrix (resid == y, ldr == ldy, resid_dtype ==
+ * y_dtype, no resid_period): every kernel loads a residual element in the workgroup that stores that element, before the store.
+ * y must not alias x, w, bias, ln_stats, ln_s or ws, and must not overlap resid in any other way. */
 int pm_linear_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
                    const void* resid, int64_t ldr, int resid_dtype, void* y, int64_t ldy, int y_dtype,
                    int64_t M, int64_t N, int64_t K, int act, void* stream);
@@ -50,7 +53,7 @@ int pm_linear_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const
  *    (x_rows_per_batch == 0: plain m * ldx).  With ldx = 2*d and K = 3*d over a zero-padded time-major buffer this
  *    IS Conv1d(d, d, 3, stride 2, padding 1) (whisper.py:19): each output row reads 3 consecutive input rows;
  *  - resid rows repeat every resid_period rows (0: no repeat), e.g. "+ pos_embs[:L]" broadcast over the batch
- *    (whisper.py:31).  Order: y = act(x w^T + bias) + resid. */
+ *    (whisper.py:31).  Order: y = act(x w^T + bias) + resid.  A periodic resid must not alias y: many tiles read each of its rows. */
 int pm_linear_bf16_ex(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w,
                       int64_t ldw, const float* bias, const void* resid, int64_t ldr, int resid_dtype,
                       int64_t resid_period, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act,
@@ -60,7 +63,7 @@ int pm_linear_bf16_ex(const void* x, int64_t ldx, int64_t x_rows_per_batch, int6
  * 2e-5, tests/audio2text/test_whisper.py:45 5e-5) and for the exact Whisper pipeline: y = act(x w^T + bias) + resid, all
  * operands f32, on the f32-input MFMA (exact fp32 products and accumulation; csrc/linear_f32.hip).  Addressing as
  * pm_linear_bf16_ex (two-level x rows: Conv1d / Conv2d windows as GEMM rows; periodic resid rows: a position table).
- * ldx, ldw multiples of 4, x and w 16-byte aligned; every activation of the table above. */
+ * ldx, ldw multiples of 4, x and w 16-byte aligned; every activation of the table above.  y must not alias x, w, bias or resid. */
 int pm_linear_f32(const float* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const float* w, int64_t ldw,
                   const float* bias, const float* resid, int64_t ldr, int64_t resid_period, float* y, int64_t ldy, int64_t M,
                   int64_t N, int64_t K, int act, void* stream);
@@ -69,7 +72,8 @@ int pm_linear_f32(const float* x, int64_t ldx, int64_t x_rows_per_batch, int64_t
  * before the first call and left alone afterwards.  With it the dispatcher may deal a GEMM's K steps out as ONE stream over
  * the persistent workgroups ("stream-K", csrc/linear_bf16_sk.hip) where whole 256 x 256 tiles would leave the last round
  * badly filled (M = 50432: N = 768 is 2.31 rounds, N = 3072 9.23); tiles shared by two workgroups are combined in fp32
- * through the workspace, deterministically.  One workspace serves one stream at a time.  ws == NULL: pm_linear_bf16_ln. */
+ * through the workspace, deterministically.  One workspace serves one stream at a time.  ws == NULL: pm_linear_bf16_ln.
+ * With a workspace resid must not alias y (a tile cut along K is finished by a workgroup other than the one that started it). */
 int pm_linear_bf16_ws(const void* x, int64_t ldx, int64_t x_rows_per_batch, int64_t x_batch_stride, const void* w, int64_t ldw,
                       const float* bias, const void* resid, int64_t ldr, int resid_dtype, int64_t resid_period, void* y,
                       int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, const float* ln_stats,
@@ -104,7 +108,8 @@ int pm_linear_ln_supported(int64_t M, int64_t N, int64_t K, int act, int produce
 
 /* nn.LayerNorm over the last dim (transformer.py:87,90,93; vit.py:69; whisper.py:27,45):
  * y[r,:] = (x[r,:] - mean) * rsqrt(var + eps) * gamma + beta, fp32 statistics, biased variance.
- * x: x_dtype (M, d) with row stride ldx; gamma/beta: f32 (d); y: y_dtype.  d % 8 == 0. */
+ * x: x_dtype (M, d) with row stride ldx; gamma/beta: f32 (d); y: y_dtype.  d % 8 == 0.  y must not alias x, gamma or beta
+ * (pm_layernorm_ex, pm_rmsnorm: nor resid). */
 int pm_layernorm(const void* x, int64_t ldx, int x_dtype, const float* gamma, const float* beta, float eps,
                  void* y, int64_t ldy, int y_dtype, int64_t M, int64_t d, void* stream);
 
@@ -634,7 +639,8 @@ int pm_attention_hd32_bf16(const void* q, int64_t q_stride_b, int64_t q_stride_t
 
 /* ---- MLP-Mixer (reference: pytorch_models/image/mlp_mixer.py; csrc/mixer.hip).
  * pm_mixer_token_mix_bf16: y = x + (W2 GELU(W1 LN(x)^T + b1) + b2)^T per image (mlp_mixer.py:30), one kernel on the bf16 MFMA.
- * x, y: bf16 (N, T, C) contiguous; y may alias x.  stats: f32 (N*T, 2) [mean, rstd] of the rows of x (pm_ln_stats_finalize or
+ * x, y: bf16 (N, T, C) contiguous; y may alias x (y == x: a workgroup stages its own image x channel slab behind a barrier and a
+ * thread loads the residual elements it stores before it stores them); y must not alias any other operand.  stats: f32 (N*T, 2) [mean, rstd] of the rows of x (pm_ln_stats_finalize or
  * pm_row_stats); gamma, beta: f32 (C), norm1; b1: f32 (Dt); b2: f32 (T).
  * w1, w2: the weights W1 (Dt, T) and W2 (T, Dt) FRAGMENT-MAJOR, bf16: a matrix W (R, K) is zero-padded to R32 = R rounded up to
  * 32 rows and K16 = K rounded up to 16 columns and stored as [R32/32 strips][K16/16 steps][64 lanes][8], lane l of strip s and

@@ -145,6 +145,67 @@ def _apart(t: Tensor) -> bool:
     return True
 
 
+def _span(t: Tensor) -> tuple[int, int]:
+    """[first byte, one past the last byte) of ``t``'s elements (attribute reads only; torch strides are never negative)"""
+    p = t.data_ptr()
+    if t.is_contiguous():
+        return p, p + t.nbytes
+    if t.numel() == 0:
+        return p, p
+    return p, p + (1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))) * t.element_size()
+
+
+def _columns_apart(a: Tensor, b: Tensor) -> bool:
+    """``a`` and ``b`` are proven to be disjoint column ranges of one row-major parent: unit last strides, one row pitch that every
+    leading stride of both is a multiple of, and column windows [0, wa) and [d, d + wb) that fit side by side in one pitch."""
+    if a.dim() < 2 or a.dim() != b.dim() or a.stride(-1) != 1 or b.stride(-1) != 1:
+        return False
+    ia, ib = a.element_size(), b.element_size()
+    lead_a = [s * ia for n, s in zip(a.shape[:-1], a.stride()[:-1]) if n > 1]
+    lead_b = [s * ib for n, s in zip(b.shape[:-1], b.stride()[:-1]) if n > 1]
+    if not lead_a or not lead_b:
+        return False
+    pitch = min(lead_a)
+    if pitch <= 0 or pitch != min(lead_b) or any(s % pitch for s in lead_a + lead_b):
+        return False
+    d, wa, wb = (b.data_ptr() - a.data_ptr()) % pitch, a.shape[-1] * ia, b.shape[-1] * ib
+    return wa <= d and d + wb <= pitch
+
+
+def _same_view(a: Tensor, b: Tensor) -> bool:
+    return a.data_ptr() == b.data_ptr() and a.dtype == b.dtype and a.shape == b.shape and a.stride() == b.stride()
+
+
+def _unaliased(who: str, wname: str, w: Tensor, names: tuple, others: tuple, may: tuple = ()) -> None:
+    """The aliasing contract for ONE caller-supplied operand ``w`` that the call writes, against every other
+    tensor operand of the call (``names`` / ``others`` in step; None entries are absent operands): no byte of ``w`` is a byte of
+    another operand.  The exception: an operand named in ``may`` - the pairs the kernels support, each "may alias" in
+    include/pm_mi355x.h - may be the very same view (pointer, dtype, shape and strides).  Anything else raises ValueError before a
+    launch.  Called after the shape and dtype checks, and only when the caller supplied ``w``: a wrapper that allocates its own
+    output runs none of this.  Attribute reads only, no device work; the contiguous path is two comparisons per operand."""
+    w0 = w.data_ptr()
+    w1 = w0 + (w.nbytes if w.is_contiguous() else _span(w)[1] - w0)
+    for i, t in enumerate(others):
+        if t is None:
+            continue
+        p = t.data_ptr()
+        if p >= w1 or (p < w0 and p + (t.nbytes if t.is_contiguous() else _span(t)[1] - p) <= w0) or w1 == w0:
+            continue
+        if t.numel() == 0 or _columns_apart(w, t) or (names[i] in may and _same_view(w, t)):
+            continue
+        raise ValueError(f"{who}: {wname} (written) shares memory with {names[i]}" + (
+            f"; {wname} may only be {names[i]} itself, as the same view" if names[i] in may else
+            ": an operand the call writes must not overlap another operand"))
+
+
+def _all_unaliased(who: str, wnames: tuple, ws: tuple, names: tuple, others: tuple) -> None:
+    """_unaliased for a call that writes several caller-supplied operands (None: not supplied): each against the written ones
+    behind it and against every other operand - two written operands never share memory."""
+    for i, w in enumerate(ws):
+        if w is not None:
+            _unaliased(who, wnames[i], w, wnames[i + 1:] + names, ws[i + 1:] + others)
+
+
 def linear_ln_supported(M: int, N: int, K: int, act: str, produce: bool) -> bool:
     return bool(lib().pm_linear_ln_supported(M, N, K, ACT[act], int(produce)))
 
@@ -226,6 +287,7 @@ def _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_ro
     N = w.shape[0]
     if bias is not None:
         _need(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N, "linear: bias must be f32 (N)")
+    given = out is not None
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype, device=x.device)
     elif not (out.is_contiguous() or _apart(out)):
@@ -248,6 +310,21 @@ def _linear_args(x, w, bias, act, resid, out_dtype, out, ln_stats, ln_s, want_ro
             _dt(resid) if resid is not None else 0, resid_period if resid is not None else 0, out.data_ptr(), out.stride(0),
             _dt(out), M, N, K, ACT[act], ln_stats.data_ptr() if ln_stats is not None else None,
             ln_s.data_ptr() if ln_s is not None else None, rows.data_ptr() if rows is not None else None, ws, ws_bytes)
+    if given:
+        # The aliasing contract on the integers the launch takes anyway: out's bytes [op, o1) against every
+        # other operand's, each extent exact (last row's end).  Whatever this cannot prove apart goes to the shared helper, which
+        # knows column ranges and the one honoured alias - resid may be out itself: every kernel reads a residual element in the
+        # workgroup that stores it, before the store; a periodic residual row is read by many tiles, and the opt-in K-cut kernels
+        # finish a tile in two workgroups - and refuses the rest.
+        xp, ldx, _, _, wp, ldw, bp, rp, ldr, rdt, _, op, ldo, odt = args[:14]
+        sp, lp = args[18], args[19]
+        o1 = op + ((M - 1) * ldo + N) * (2 if odt == PM_BF16 else 4)
+        if not ((xp >= o1 or xp + ((M - 1) * ldx + K) * 2 <= op) and (wp >= o1 or wp + ((N - 1) * ldw + K) * 2 <= op)
+                and (bp is None or bp >= o1 or bp + 4 * N <= op)
+                and (rp is None or rp >= o1 or rp + (((resid_period or M) - 1) * ldr + N) * (2 if rdt == PM_BF16 else 4) <= op)
+                and (sp is None or sp >= o1 or sp + 8 * M <= op) and (lp is None or lp >= o1 or lp + 4 * N <= op)):
+            _unaliased("linear", "out", out, ("x", "w", "bias", "resid", "ln_stats", "ln_s"), (x, w, bias, resid, ln_stats, ln_s),
+                       ("resid",) if resid_period == 0 and not _USE_WS else ())
     return args, out, rows
 
 
@@ -284,11 +361,14 @@ def linear_f32(x: Tensor, w: Tensor, bias: Tensor | None = None, *, act: str = "
     if resid is not None:
         _need(resid.dtype == torch.float32 and resid.dim() == 2 and resid.shape[1] == N and resid.stride(1) == 1
               and resid.shape[0] >= (resid_period or M), "linear_f32: resid must be f32 (rows, N)")
+    given = out is not None
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=w.device)
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("linear_f32: rows of out overlap")
     _need(out.dtype == torch.float32 and out.shape == (M, N) and out.stride(1) == 1, "linear_f32: bad out")
+    if given:
+        _unaliased("linear_f32", "out", out, ("x", "w", "bias", "resid"), (x, w, bias, resid))
     if _empty("linear_f32", M, N, K):
         return out
     rc = _launch("linear_f32", 2.0 * M * N * K, lambda: lib().pm_linear_f32(
@@ -340,6 +420,7 @@ def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, 
               and gamma.is_contiguous() and beta.is_contiguous(), "layernorm: gamma / beta must be contiguous f32 (d)")
     if resid is not None:
         _need(resid.shape == x.shape and resid.stride(1) == 1, "layernorm: resid must be (M, d), row-major")
+    given = out is not None
     if out is None:
         out = torch.empty((M, d), dtype=out_dtype or x.dtype, device=x.device)
     elif not (out.is_contiguous() or _apart(out)):
@@ -348,6 +429,27 @@ def layernorm(x: Tensor, gamma: Tensor | None, beta: Tensor | None, eps: float, 
     if _empty("layernorm", M, d):
         return out
     gp, bp = (gamma.data_ptr(), beta.data_ptr()) if gamma is not None else (None, None)
+    if given:  # a caller's out: every pointer and stride fetched once, for the aliasing check and for the launch; a call that lets
+        # layernorm() allocate its result runs the code below, unchanged
+        xp, ldx, xdt, ex, op, ldo, odt, eo = x.data_ptr(), x.stride(0), _dt(x), x.element_size(), out.data_ptr(), out.stride(0), _dt(out), out.element_size()
+        rp, ldr, rdt, er = (resid.data_ptr(), resid.stride(0), _dt(resid), resid.element_size()) if resid is not None else (None, 0, 0, 0)
+        # the aliasing contract on the integers the launch takes anyway: out's bytes [op, o1) against every other
+        # operand's exact extent; what this cannot prove apart goes to the shared helper (column ranges of one parent, the refusal)
+        m1 = M - 1
+        o1 = op + (m1 * ldo + d) * eo
+        if not ((xp >= o1 or xp + (m1 * ldx + d) * ex <= op)
+                and (gp is None or ((gp >= o1 or gp + 4 * d <= op) and (bp >= o1 or bp + 4 * d <= op)))
+                and (rp is None or rp >= o1 or rp + (m1 * ldr + d) * er <= op)):
+            _unaliased("layernorm", "out", out, ("x", "gamma", "beta", "resid"), (x, gamma, beta, resid))
+        nbytes = float(M * d * (ex + eo + er))
+        if act == "none" and resid is None and gamma is not None:
+            largs = (xp, ldx, xdt, gp, bp, float(eps), op, ldo, odt, M, d)  # (one closure variable: the plain path's cells stay as they were)
+            rc = _launch("layernorm", nbytes, lambda: lib().pm_layernorm(*largs, _stream()))
+        else:
+            largs = (xp, ldx, xdt, gp, bp, float(eps), ACT[act], rp, ldr, rdt, op, ldo, odt, M, d)
+            rc = _launch("layernorm", nbytes, lambda: lib().pm_layernorm_ex(*largs, _stream()))
+        check(rc, f"pm_layernorm(M={M}, d={d})")
+        return out
     nbytes = float(M * d * (x.element_size() + out.element_size() + (resid.element_size() if resid is not None else 0)))
     if act == "none" and resid is None and gamma is not None:
         rc = _launch("layernorm", nbytes, lambda: lib().pm_layernorm(
@@ -404,6 +506,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
     hd = D // n_heads
     for t in (q, k, v):
         _need(t.dtype == torch.bfloat16 and t.stride(2) == 1, "attention: bf16 operands with unit last stride")
+    given = out is not None
     if out is None:
         out = torch.empty((B, Lq, D), dtype=torch.bfloat16, device=q.device)
     elif not (out.is_contiguous() or _apart(out)):
@@ -412,6 +515,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
     args = (q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0),
             v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, n_heads, Lq, Lk, int(causal))
     sb = sh = sq = 0
+    bp = None
     empty = _empty("attention", B * Lq, Lk, D)
     if bias is not None:
         _need(bias.dim() == 4 and bias.dtype == torch.float32 and bias.shape[2:] == (Lq, Lk) and bias.stride(3) == 1
@@ -419,16 +523,28 @@ def attention(q: Tensor, k: Tensor, v: Tensor, n_heads: int, causal: bool = Fals
         sb = 0 if bias.shape[0] == 1 else bias.stride(0)
         sh = 0 if bias.shape[1] == 1 else bias.stride(1)
         sq = bias.stride(2)
+        bp = bias.data_ptr()
     if empty:
         return out
+    if given:
+        # the aliasing contract on the integers the launch takes anyway: out's bytes [op, oe) against the exact
+        # extents of q, k, v and the bias (sb / sh are 0 for a broadcast dimension); whatever this cannot prove apart (column slices
+        # of one packed projection) goes to the shared helper, which refuses what overlaps
+        qp, q0, q1, kp, k0, k1, vp, v0, v1, op, o0, o1 = args[:12]
+        b1, l1, m1 = B - 1, Lq - 1, Lk - 1
+        oe = op + (b1 * o0 + l1 * o1 + D) * 2
+        if not ((qp >= oe or qp + (b1 * q0 + l1 * q1 + D) * 2 <= op) and (kp >= oe or kp + (b1 * k0 + m1 * k1 + D) * 2 <= op)
+                and (vp >= oe or vp + (b1 * v0 + m1 * v1 + D) * 2 <= op)
+                and (bp is None or bp >= oe or bp + (b1 * sb + (n_heads - 1) * sh + l1 * sq + Lk) * 4 <= op)):
+            _unaliased("attention", "out", out, ("q", "k", "v", "bias"), (q, k, v, bias))
     if hd != 64:
         rc = _launch("attention_generic", 4.0 * B * n_heads * Lq * Lk * hd, lambda: lib().pm_attention_generic_bf16(
-            *args[:16], hd, int(causal), bias.data_ptr() if bias is not None else None, sb, sh, sq, _stream()))
+            *args[:16], hd, int(causal), bp, sb, sh, sq, _stream()))
     elif bias is None:
         rc = _launch("attention_bf16", 4.0 * B * n_heads * Lq * Lk * 64, lambda: lib().pm_attention_bf16(*args, _stream()))
     else:
         rc = _launch("attention_bf16", 4.0 * B * n_heads * Lq * Lk * 64, lambda: lib().pm_attention_bias_bf16(
-            *args, bias.data_ptr(), sb, sh, sq, _stream()))
+            *args, bp, sb, sh, sq, _stream()))
     check(rc, f"pm_attention_bf16(B={B}, H={n_heads}, Lq={Lq}, Lk={Lk})")
     return out
 
@@ -538,6 +654,7 @@ def _linear_strided_args(x, M, K, row_stride, rows_per_batch, batch_stride, w, b
     else:  # e.g. a column slice of a wider matrix (one group of a grouped conv)
         _need(out.shape == (M, N) and out.stride(1) == 1 and (out.is_cuda or not x.is_cuda) and _apart(out),
               "linear_strided: out must be (M, N) with unit column stride and rows that do not overlap")
+        _unaliased("linear_strided", "out", out, ("x", "w", "bias", "resid"), (x, w, bias, resid))
     ws, ws_bytes = _ws_args(M, out.device) if out.is_cuda else (None, 0)
     args = (x.data_ptr(), row_stride, rows_per_batch, batch_stride, w.data_ptr(), w.stride(0),
             bias.data_ptr() if bias is not None else None, resid.data_ptr() if resid is not None else None,
@@ -780,9 +897,12 @@ def embed_tokens(tokens: Tensor, emb: Tensor, pos: Tensor | None, pos0: int = 0,
                                        B, L, pos0, d, V, _stream())
         check(rc, f"pm_embed_tokens_f32(B={B}, L={L}, d={d})")
         return out
+    given = out is not None
     if out is None:
         out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
     _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens: out must be contiguous (B, L, d)")
+    if given:
+        _unaliased("embed_tokens", "out", out, ("tokens", "emb", "pos"), (tokens, emb, pos))
     if empty:
         return out
     rc = lib().pm_embed_tokens(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr() if pos is not None else None, out.data_ptr(), _dt(out), B, L, pos0, d, V,
@@ -906,12 +1026,17 @@ def prefill_attention(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, p0: int
         _need(t.dtype == torch.bfloat16, "prefill_attention: bf16 operands (fp32 caches keep the token-by-token prompt)")
     C = qkv.shape[0] // B if B else 0
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
+    given = out is not None
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("prefill_attention: rows of out overlap")
     _need(_apart(kc) and _apart(vc), "prefill_attention: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention: out must be bf16 (B * C, H * 64)")
+    _unaliased("prefill_attention", "kc", kc, ("qkv", "vc"), (qkv, vc))  # the caches are always the caller's
+    _unaliased("prefill_attention", "vc", vc, ("qkv",), (qkv,))
+    if given:
+        _unaliased("prefill_attention", "out", out, ("qkv", "kc", "vc"), (qkv, kc, vc))
     if _empty("prefill_attention", B, H, T):
         return out
     kv = plan.cache_kv(kc, vc)
@@ -954,12 +1079,17 @@ def prefill_attention_ragged(qkv: Tensor, kc: Tensor, vc: Tensor, n_heads: int, 
     _key_start(key_start, B, "prefill_attention_ragged")
     C = qkv.shape[0] // B if B else 0
     _need(0 <= p0 and p0 + C <= T <= 4096, f"prefill_attention_ragged: positions {p0} .. {p0 + C - 1} do not fit caches of {T} (<= 4096) keys")
+    given = out is not None
     if out is None:
         out = torch.empty((B * C, H * 64), dtype=torch.bfloat16, device=qkv.device)
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("prefill_attention_ragged: rows of out overlap")
     _need(_apart(kc) and _apart(vc), "prefill_attention_ragged: cache rows overlap")
     _need(out.shape == (B * C, H * 64) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "prefill_attention_ragged: out must be bf16 (B * C, H * 64)")
+    _unaliased("prefill_attention_ragged", "kc", kc, ("qkv", "vc", "key_start"), (qkv, vc, key_start))  # the caches are always the caller's
+    _unaliased("prefill_attention_ragged", "vc", vc, ("qkv", "key_start"), (qkv, key_start))
+    if given:
+        _unaliased("prefill_attention_ragged", "out", out, ("qkv", "kc", "vc", "key_start"), (qkv, kc, vc, key_start))
     if _empty("prefill_attention_ragged", B, H, T):
         return out
     kv = plan.cache_kv(kc, vc)
@@ -986,9 +1116,12 @@ def embed_tokens_ragged(tokens: Tensor, emb: Tensor, pos: Tensor, key_start: Ten
             raise IndexError(f"embed_tokens_ragged: token id {bad} outside the vocabulary [0, {V})")
     _need(pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d and pos.shape[0] >= pos0 + L,
           f"embed_tokens_ragged: need {pos0 + L} position rows, have {pos.shape[0]}")
+    given = out is not None
     if out is None:
         out = torch.empty((B, L, d), dtype=out_dtype, device=emb.device)
     _need(out.shape == (B, L, d) and out.is_contiguous(), "embed_tokens_ragged: out must be contiguous (B, L, d)")
+    if given:
+        _unaliased("embed_tokens_ragged", "out", out, ("tokens", "emb", "pos", "key_start"), (tokens, emb, pos, key_start))
     if empty:
         return out
     rc = lib().pm_embed_tokens_ragged(tokens.data_ptr(), emb.data_ptr(), pos.data_ptr(), key_start.data_ptr(), out.data_ptr(), _dt(out),
@@ -1024,7 +1157,12 @@ def _tail_state(what: str, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tokens:
     _need(emb.dtype == torch.bfloat16 and emb.is_contiguous() and pos_tab.dtype == torch.float32 and pos_tab.is_contiguous()
           and pos_tab.shape[1] == emb.shape[1], f"{what}: bf16 table, f32 positions")
     _rows(what, B, prompt.shape[1], tokens.shape[1], emb.shape[0], emb.shape[1], pos_tab.shape[0])
-    # (a validation that reads *pos back: not under capture, where the position is whatever the replay finds there)
+
+
+def _tail_pos(what: str, pos: Tensor, pos_tab: Tensor) -> None:
+    """the one check of the tail's state that reads a VALUE (behind the aliasing check: a position that shares memory with another
+    operand holds whatever that operand holds).  It reads *pos back: not under capture, where the position is whatever the replay
+    finds there."""
     _need(capturing() or 0 <= int(pos) + 1 < pos_tab.shape[0], f"{what}: the positional table must cover position + 1")
 
 
@@ -1042,6 +1180,9 @@ def dec_next_token(ws_val: Tensor, ws_idx: Tensor, pos: Tensor, prompt: Tensor, 
     _rows("dec_next_token", B, ws_val.shape[1])
     _need(margins is None or (margins.dtype == torch.float32 and margins.shape == tokens.shape and margins.is_contiguous()),
           "dec_next_token: margins f32 like tokens")
+    _all_unaliased("dec_next_token", ("pos", "tok_cur", "tokens", "ticket", "margins"), (pos, tok_cur, tokens, ticket, margins),
+                   ("ws_val", "ws_idx", "prompt", "emb", "pos_tab", "key_start"), (ws_val, ws_idx, prompt, emb, pos_tab, key_start))
+    _tail_pos("dec_next_token", pos, pos_tab)
     x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
     if key_start is None:
         args = (ws_val.data_ptr(), ws_idx.data_ptr(), ws_val.shape[1], pos.data_ptr(), prompt.data_ptr(), P, tok_cur.data_ptr(),
@@ -1064,6 +1205,9 @@ def dec_sample_topk(logits: Tensor, k: int, seed: int, pos: Tensor, prompt: Tens
     V, d = emb.shape
     _need(logits.dtype == torch.float32 and logits.shape == (B, V) and logits.stride(1) == 1 and 1 <= k <= min(64, V),
           "dec_sample_topk: logits f32 (B, V), 1 <= k <= 64")
+    _all_unaliased("dec_sample_topk", ("pos", "tok_cur", "tokens", "ticket"), (pos, tok_cur, tokens, ticket),
+                   ("logits", "prompt", "emb", "pos_tab", "key_start"), (logits, prompt, emb, pos_tab, key_start))
+    _tail_pos("dec_sample_topk", pos, pos_tab)
     x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
     if key_start is None:
         args = (logits.data_ptr(), logits.stride(0), V, k, int(seed) & (2**64 - 1), pos.data_ptr(), prompt.data_ptr(), P, tok_cur.data_ptr(),
@@ -1089,6 +1233,7 @@ def dec_whisper_rules(logits: Tensor, tokens: Tensor, pos: Tensor, P: int, *, eo
           "dec_whisper_rules: tokens int64 (B, Ttot)")
     _need(pos.dtype == torch.int32 and pos.numel() == 1, "dec_whisper_rules: pos is one device int32")
     _rows("dec_whisper_rules", logits.shape[0], logits.shape[1], tokens.shape[1])
+    _unaliased("dec_whisper_rules", "logits", logits, ("tokens", "pos"), (tokens, pos))
     i32 = dict(dtype=torch.int32, device=logits.device)
     sup, blk = torch.tensor(list(suppress), **i32), torch.tensor(list(blank), **i32)
     B, V = logits.shape
@@ -1152,11 +1297,17 @@ def dec_beam_select(cand_score: Tensor, cand_tok: Tensor, scores: Tensor, finish
     _need(pos.dtype == torch.int32 and pos.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1,
           "dec_beam_select: pos and ticket are one device int32 each")
     _rows("dec_beam_select", B, W, V, d, tokens.shape[1], prompt.shape[1])
+    _all_unaliased("dec_beam_select", ("scores", "finished", "parents", "tokens", "pos", "tok_cur", "x", "ticket"),
+                   (scores, finished, parents, tokens, pos, tok_cur, x, ticket),
+                   ("cand_score", "cand_tok", "prompt", "emb", "pos_tab"), (cand_score, cand_tok, prompt, emb, pos_tab))
     rc = lib().pm_dec_beam_select(cand_score.data_ptr(), cand_tok.data_ptr(), W, scores.data_ptr(), finished.data_ptr(),
                                   parents.data_ptr(), -1 if eos is None else eos, tokens.data_ptr(), tokens.shape[1], pos.data_ptr(),
                                   prompt.data_ptr(), prompt.shape[1], tok_cur.data_ptr(), emb.data_ptr(), pos_tab.data_ptr(),
                                   x.data_ptr(), d, V, ticket.data_ptr(), B, _stream())
     check(rc, f"pm_dec_beam_select(B={B}, W={W})")
+
+
+_CACHE_NAMES = tuple("caches[%d]" % i for i in range(128))  # the operand names of dec_beam_reorder's refusals, built once
 
 
 def dec_beam_reorder(caches: list[Tensor], parents: Tensor, pos: Tensor) -> None:
@@ -1176,6 +1327,8 @@ def dec_beam_reorder(caches: list[Tensor], parents: Tensor, pos: Tensor) -> None
     for c in caches:
         _need(c.shape == c0.shape and c.dtype == c0.dtype and c.is_contiguous() and c.data_ptr() % 16 == 0,
               "dec_beam_reorder: caches of one geometry, contiguous, 16-byte aligned")
+    _all_unaliased("dec_beam_reorder", _CACHE_NAMES[:len(caches)] if len(caches) <= len(_CACHE_NAMES) else
+                   tuple("caches[%d]" % i for i in range(len(caches))), tuple(caches), ("parents", "pos"), (parents, pos))
     table = torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64, device=c0.device)
     rc = lib().pm_dec_beam_reorder(table.data_ptr(), len(caches), parents.data_ptr(), pos.data_ptr(), B, W, c0.shape[1], c0.shape[2],
                                    int(c0.dtype == torch.float32), _stream())
@@ -1293,11 +1446,14 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, N: int, H: int, W: int, n_
     if bias is not None:
         _need(bias.dtype == torch.float32 and bias.shape == (n_heads, L, L) and bias.is_contiguous(),
               f"window_attention: bias must be contiguous f32 ({n_heads}, {L}, {L})")
+    given = out is not None
     if out is None:
         out = torch.empty((M, D), dtype=torch.bfloat16, device=q.device)
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("window_attention: rows of out overlap")
     _need(out.dtype == torch.bfloat16 and out.shape[0] == M and out.shape[1] >= D and out.stride(1) == 1, "window_attention: bad out")
+    if given:
+        _unaliased("window_attention", "out", out, ("q", "k", "v", "bias"), (q, k, v, bias))
     if _empty("window_attention", N, H, W, n_heads, ws):
         return out
     nbytes = float(M * D * 2 * 4)
@@ -1541,9 +1697,14 @@ def mixer_token_mix(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, w1f: 
     _f32vec(beta, C, "mixer_token_mix: beta")
     _f32vec(b1, Dt, "mixer_token_mix: b1")
     _f32vec(b2, T, "mixer_token_mix: b2")
+    given = out is not None
     if out is None:
         out = torch.empty_like(x)
     _need(out.shape == x.shape and out.dtype == torch.bfloat16 and out.is_contiguous(), "mixer_token_mix: out must be like x")
+    if given:  # out may be x itself: a workgroup stages its own (image, channel slab) of x in LDS behind a barrier, then every
+        # thread reads the residual elements it stores before it stores them (csrc/mixer.hip, phases 0 and 2)
+        _unaliased("mixer_token_mix", "out", out, ("x", "stats", "gamma", "beta", "w1f", "b1", "w2f", "b2"),
+                   (x, stats, gamma, beta, w1f, b1, w2f, b2), ("x",))
     rows = torch.empty((N * T, C // 64, 2), dtype=torch.float32, device=x.device) if want_row_stats else None
     if _empty("mixer_token_mix", N, T, C, Dt):
         return (out, rows) if want_row_stats else out
@@ -1725,6 +1886,7 @@ def groupnorm1_(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, resid: Tenso
         _need(resid.shape == x.shape, "groupnorm1_: resid must have x's shape")
         _f32c(resid, "groupnorm1_: resid")
     _need(B <= 65535 and T >= 1, "groupnorm1_: at most 65535 clips, at least one frame")
+    _unaliased("groupnorm1_", "x", x, ("gamma", "beta", "resid"), (gamma, beta, resid))
     if _empty("groupnorm1_", B, T, C):
         return x
     work = torch.empty((lib().pm_groupnorm1_workspace_doubles(B, T * C),), dtype=torch.float64, device=x.device)
@@ -1844,6 +2006,7 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
         if bool(bad.any()):
             raise IndexError(f"lm_score: target id {targets[bad][0].item()} outside [-1, {V})")
     dev = h.device
+    given_out = out
     if out is None:
         out = torch.empty(M, dtype=torch.float32, device=dev)
     _need(out.dtype == torch.float32 and out.shape == (M,) and out.is_contiguous(), "lm_score: out must be contiguous f32 (M,)")
@@ -1857,9 +2020,13 @@ def lm_score(h: Tensor, w: Tensor, targets: Tensor, *, want_lse: bool = False, w
     if _empty("lm_score", M, V, K):
         return res[0] if len(res) == 1 else res
     nws = lm_score_ws_bytes(M, V)
+    given_ws = ws
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws, f"lm_score: ws must hold {nws} bytes")
+    if given_out is not None or lse_out is not None or argmax_out is not None or given_ws is not None:
+        _all_unaliased("lm_score", ("out", "lse_out", "argmax_out", "ws"), (given_out, lse_out, argmax_out, given_ws),
+                       ("h", "w", "targets"), (h, w, targets))
     nbytes = float(2 * (h.numel() + w.numel()) + nws + 8 * M + 4 * M)
     rc = _launch("lm_score", (2.0 * M * V * K, nbytes), lambda: lib().pm_lm_score_bf16(
         h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), targets.data_ptr(), out.data_ptr(),
@@ -1910,9 +2077,12 @@ def align_lse(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: Tens
     selected head; rows t >= len_b are not written."""
     B, L, S, H, nh = _align_qk("align_lse", q, k, heads, lengths, frames)
     _cuda(q, out)
+    given = out is not None
     if out is None:
         out = torch.empty((B, nh, L), dtype=torch.float32, device=q.device)
     _need(out.dtype == torch.float32 and out.shape == (B, nh, L) and out.is_contiguous(), f"align_lse: out must be contiguous f32 {(B, nh, L)}")
+    if given:
+        _unaliased("align_lse", "out", out, ("q", "k", "heads", "lengths", "frames"), (q, k, heads, lengths, frames))
     if _empty("align_lse", B, L, S, nh):
         return out
     rc = _launch("align_lse", (2.0 * B * nh * L * S * 64, float(2 * B * nh * (L + S) * 64)), lambda: lib().pm_align_lse_bf16(
@@ -1933,6 +2103,7 @@ def align_matrix(q: Tensor, k: Tensor, heads: Tensor, lengths: Tensor, frames: T
     _need(lse.dtype == torch.float32 and lse.shape == (B, nh, L) and lse.is_contiguous(), f"align_matrix: lse must be contiguous f32 {(B, nh, L)}")
     _need(m.dtype == torch.float32 and m.shape == (B, L, S) and m.stride(2) == 1 and m.stride(1) >= S and _apart(m),
           f"align_matrix: m must be f32 {(B, L, S)} with a unit last stride and rows that do not overlap")
+    _unaliased("align_matrix", "m", m, ("q", "k", "heads", "lengths", "frames", "lse"), (q, k, heads, lengths, frames, lse))
     if _empty("align_matrix", B, L, S, nh):
         return m
     rc = _launch("align_matrix", (2.0 * B * nh * L * S * 64, float(4 * B * L * S)), lambda: lib().pm_align_matrix_bf16(
@@ -1958,16 +2129,20 @@ def align_dtw(m: Tensor, lengths, frames, skip_first: int = 0, skip_last: int = 
     lengths = align_counts(lengths, B, 1, L, "align_dtw: lengths", m.device)
     frames = align_counts(frames, B, 4, S, "align_dtw: frames", m.device)
     _cuda(m, lengths, frames, out, ws)
+    given_out = out
     if out is None:
         out = torch.empty((B, L), dtype=torch.int32, device=m.device)
     _need(out.dtype == torch.int32 and out.shape == (B, L) and out.is_contiguous(), f"align_dtw: out must be contiguous int32 {(B, L)}")
     if _empty("align_dtw", B, L, S):
         return out
     nws = align_ws_bytes(B, L, S)
+    given_ws = ws
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=m.device)
     _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws and ws.data_ptr() % 8 == 0,
           f"align_dtw: ws must hold {nws} bytes, 8-byte aligned")
+    if given_out is not None or given_ws is not None:
+        _all_unaliased("align_dtw", ("out", "ws"), (given_out, given_ws), ("m", "lengths", "frames"), (m, lengths, frames))
     rc = _launch("align_dtw", (float(B * L * S), float(4 * B * L * S + nws)), lambda: lib().pm_align_dtw_f32(
         m.data_ptr(), m.stride(1), m.stride(0), lengths.data_ptr(), frames.data_ptr(), out.data_ptr(), ws.data_ptr(), B, L, S,
         skip_first, skip_last, _stream()))
@@ -2038,11 +2213,14 @@ def attention_varlen(q: Tensor, k: Tensor, v: Tensor, n_heads: int, seq: SeqLens
     _need(n_heads >= 1 and D == n_heads * 64, f"attention_varlen: head_dim 64 only (width {D}, {n_heads} heads)")
     for t in (q, k, v):
         _need(t.dtype == torch.bfloat16 and t.stride(1) == 1, "attention_varlen: bf16 operands with unit last stride")
+    given = out is not None
     if out is None:
         out = torch.empty((T, D), dtype=torch.bfloat16, device=q.device)
     elif not (out.is_contiguous() or _apart(out)):
         raise ValueError("attention_varlen: rows of out overlap")
     _need(out.shape == (T, D) and out.dtype == torch.bfloat16 and out.stride(1) == 1, "attention_varlen: out must be bf16 (T_total, H*64)")
+    if given:
+        _unaliased("attention_varlen", "out", out, ("q", "k", "v", "seq.cu", "rel_lut"), (q, k, v, seq.cu, rel_lut))
     if T == 0:
         return out
     work = 4.0 * n_heads * 64 * sum(n * n for n in seq.lengths)
@@ -2133,6 +2311,7 @@ def rows_zero_tail(x: Tensor, seq: SeqLens) -> Tensor:
     _seq(seq, "rows_zero_tail", x)
     B, L, d = _padded(x, seq, "rows_zero_tail")
     _need(_apart(x), "rows_zero_tail: rows of x overlap")
+    _unaliased("rows_zero_tail", "x", x, ("seq.cu",), (seq.cu,))
     if _empty("rows_zero_tail", B * L, d):
         return x
     rc = _launch("rows_zero_tail", (0.0, float(B * L - seq.total) * d * x.element_size()), lambda: lib().pm_rows_zero_tail(
@@ -2187,6 +2366,7 @@ def ctc_head(h: Tensor, w: Tensor, bias: Tensor | None = None, *, want_best_logp
     if bias is not None:
         _need(bias.dtype == torch.float32 and bias.shape == (V,) and bias.is_contiguous(), f"ctc_head: bias must be contiguous f32 ({V},)")
     dev = h.device
+    given_out = out
     if out is None:
         out = torch.empty((M, V), dtype=torch.float32, device=dev)
     _need(out.dtype == torch.float32 and out.shape == (M, V) and out.stride(1) == 1 and (out.stride(0) >= V or M == 1),
@@ -2196,6 +2376,8 @@ def ctc_head(h: Tensor, w: Tensor, bias: Tensor | None = None, *, want_best_logp
     blp = best_logp_out if best_logp_out is not None else (torch.empty(M, dtype=torch.float32, device=dev) if want_best_logp else None)
     if blp is not None:
         _need(blp.dtype == torch.float32 and blp.shape == (M,) and blp.is_contiguous(), "ctc_head: best_logp_out must be contiguous f32 (M,)")
+    if given_out is not None or best_out is not None or best_logp_out is not None:
+        _all_unaliased("ctc_head", ("out", "best_out", "best_logp_out"), (given_out, best_out, best_logp_out), ("h", "w", "bias"), (h, w, bias))
     if _empty("ctc_head", M, V, K):
         return out, best, blp
     ldl = max(out.stride(0), V)
@@ -2269,10 +2451,13 @@ def ctc_forward(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, bla
     0 <= U_b <= Umax) or a device int32 (B) -> loglik f32 (B) = log p(target_b | clip_b) by the alpha recursion in log space;
     exactly -inf for a pair with too few frames.  Target ids are NOT validated here (the kernel clamps them)."""
     T, V, B, Umax, tl = _ctc_rec("ctc_forward", logp, seq, targets, target_lengths, blank)
+    given = out is not None
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=logp.device)
     _cuda(out)
     _need(out.dtype == torch.float32 and out.shape == (B,) and out.is_contiguous(), f"ctc_forward: out must be contiguous f32 ({B},)")
+    if given:
+        _unaliased("ctc_forward", "out", out, ("logp", "seq.cu", "targets", "target_lengths"), (logp, seq.cu, targets, tl))
     if _empty("ctc_forward", B, V):
         return out
     rc = _launch("ctc_forward", (float(T * (2 * Umax + 1)), float(4 * T * (Umax + 1))), lambda: lib().pm_ctc_forward_f32(
@@ -2296,11 +2481,14 @@ def ctc_viterbi(logp: Tensor, seq: SeqLens, targets: Tensor, target_lengths, bla
     if _empty("ctc_viterbi", B, V):
         return start, stop, score
     nws = ctc_ws_bytes(B, Tmax, Umax)
+    given = ws is not None
     if ws is None:
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     _cuda(ws)
     _need(ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nws and ws.data_ptr() % 16 == 0,
           f"ctc_viterbi: ws must hold {nws} bytes, 16-byte aligned")
+    if given:
+        _unaliased("ctc_viterbi", "ws", ws, ("logp", "seq.cu", "targets", "target_lengths"), (logp, seq.cu, targets, tl))
     rc = _launch("ctc_viterbi", (float(T * (2 * Umax + 1)), float(4 * T * (Umax + 1) + nws)), lambda: lib().pm_ctc_viterbi_f32(
         logp.data_ptr(), max(logp.stride(0), V), seq.cu.data_ptr(), targets.data_ptr() if Umax else None, max(targets.stride(0), Umax),
         tl.data_ptr(), start.data_ptr() if Umax else None, stop.data_ptr() if Umax else None, score.data_ptr(), ws.data_ptr(),

@@ -10,7 +10,7 @@ import torch
 from torch import Tensor
 
 from . import decode_plan as plan, lib
-from .ops import _cuda, _key_start, _need, _stream, _tail_state
+from .ops import _all_unaliased, _cuda, _key_start, _need, _stream, _tail_pos, _tail_state
 
 
 def check_sampling(what: str, topk: int, temperature: float, top_p: float) -> None:
@@ -54,6 +54,9 @@ def dec_sample(logits: Tensor, pos: Tensor, prompt: Tensor, tok_cur: Tensor, tok
     _need(d % 8 == 0, "dec_sample: d_model must be a multiple of 8")
     _need(logprobs is None or (logprobs.dtype == torch.float32 and logprobs.shape == tokens.shape and logprobs.is_contiguous()),
           "dec_sample: logprobs f32, contiguous, shaped like tokens")
+    _all_unaliased("dec_sample", ("pos", "tok_cur", "tokens", "ticket", "logprobs"), (pos, tok_cur, tokens, ticket, logprobs),
+                   ("logits", "prompt", "emb", "pos_tab", "key_start"), (logits, prompt, emb, pos_tab, key_start))
+    _tail_pos("dec_sample", pos, pos_tab)
     x = torch.empty(B, d, dtype=torch.float32, device=emb.device)
     if key_start is None:
         plan.call(lib().pm_dec_sample, plan.sample_args(logits, topk, temperature, top_p, seed, pos, prompt, tok_cur, tokens, logprobs, emb,
